@@ -6,12 +6,13 @@ accumulation, dropout 0.1 as in the reference's train mode, teacher-forced CE ov
 clip_grad_norm(1.0) + AdamW + linear LR schedule; B=128 images per GPU (config.yml training.batch_size).
 Weights are the deterministic random init of that architecture (no checkpoints offline); data are synthetic.
 
-value = training images/s over all ranks. Also reported: greedy captions/s (50-token KV-cached decode,
-B=128 per GPU = config.yml validation.batch_size), the GEMM roofline (per-launch HIP-event timing of every MFMA
-GEMM of one step; algorithmic FLOPs), and the CPU baseline (oracle restatement of the reference step on a bounded
-sample, rank 0 only).
+value = training images/s over all ranks. A plain run does only what that figure needs: set-up, warm-up, the timed
+steps, the --dump-outputs files if asked for, and the JSON line. With --full also reported: greedy captions/s
+(50-token KV-cached decode, B=128 per GPU = config.yml validation.batch_size), the GEMM roofline (per-launch
+HIP-event timing of every MFMA GEMM of one step; algorithmic FLOPs), the other decode modes, precisions and batch
+sizes, and the CPU baseline (oracle restatement of the reference step on a bounded sample, rank 0 only).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     N>1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 
@@ -527,11 +528,15 @@ def replay_roofline(trainer, dom, reps=20):
 
 
 def train_rate(trainer, B, steps, warmup, use_graph, world, dev, detail=False):
-    """images/s over `steps` graph-replayed steps after `warmup` (barrier + synchronize on both sides, max over
-    ranks), the per-step median (HIP events between the steps on the launch stream), and the GEMM roofline of one
-    eager step (HIP events around every GEMM / GPT-2-block attention launch)."""
-    from icap import ops
+    """timed_steps, then gemm_roofline of the same trainer: one dict with the fields of both."""
+    r = timed_steps(trainer, B, steps, warmup, use_graph, world, dev)
+    r.update(gemm_roofline(trainer, use_graph, detail))
+    return r
 
+
+def timed_steps(trainer, B, steps, warmup, use_graph, world, dev):
+    """images/s over `steps` graph-replayed steps after `warmup` (barrier + synchronize on both sides, max over
+    ranks) and the per-step median (HIP events between the steps on the launch stream)."""
     dist = world > 1
     for _ in range(max(warmup, 1)):
         trainer.micro_step(use_graph=use_graph)
@@ -562,6 +567,15 @@ def train_rate(trainer, B, steps, warmup, use_graph, world, dev, detail=False):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = float(t.item())
     loss = float(trainer.last_loss.item())
+    return {"el": el, "loss": loss, "images_per_s": world * B * steps / el, "ms_per_step": el / steps * 1e3,
+            "median_ms": median_ms, "rank_ms": rank_ms}
+
+
+def gemm_roofline(trainer, use_graph, detail=False):
+    """The GEMM roofline of one more eager step (HIP events around every GEMM / GPT-2-block attention launch), and
+    the in-replay kernel times by difference (replay_roofline). Runs a train step of its own: after the timed ones."""
+    from icap import ops
+
     timer = GemmTimer()
     ops.GEMM_TIMER = timer
     torch.cuda.synchronize()
@@ -597,9 +611,7 @@ def train_rate(trainer, B, steps, warmup, use_graph, world, dev, detail=False):
         achieved = fl / (ms * 1e-3) / 1e12
         if rep["block_ms"] > 0 and rep["block_launches"] == bn:
             bms = rep["block_ms"]
-    return {"el": el, "loss": loss, "images_per_s": world * B * steps / el, "ms_per_step": el / steps * 1e3,
-            "eager_roofline": eager, "replay_roofline": rep,
-            "median_ms": median_ms, "rank_ms": rank_ms, "seg_ms": seg_ms, "seg_bytes": seg_bytes,
+    return {"eager_roofline": eager, "replay_roofline": rep, "seg_ms": seg_ms, "seg_bytes": seg_bytes,
             "dom": dom, "n_l": n_l, "fl": fl, "ms": ms, "achieved": achieved,
             "frac": achieved / kernel_peak(dom), "gemm_ms": sum(v[2] for v in agg.values()),
             "all_fl": sum(v[1] for v in agg.values()), "eager_ms": eager_ms, "eager_host_ms": host_ms,
@@ -679,6 +691,67 @@ def unfrozen_rate(B, dev, world, steps=10):
     return res
 
 
+def roofline_fields(r, traffic, traffic_src):
+    """The result line's "roofline" entry from gemm_roofline's figures and the committed PMC traffic of its kernel."""
+    dom, n_l, fl, ms, achieved = r["dom"], r["n_l"], r["fl"], r["ms"], r["achieved"]
+    gemm_ms, all_fl, eager_ms = r["gemm_ms"], r["all_fl"], r["eager_ms"]
+    return {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 1),
+            "peak": kernel_peak(dom), "unit": "TFLOP/s", "frac": round(achieved / kernel_peak(dom), 4),
+            "traffic": traffic, "traffic_unit": "bytes/launch (HBM, rocprofv3 PMC: 2 x FETCH_SIZE + WRITE_SIZE)",
+            "traffic_source": traffic_src, "launches_per_step": n_l,
+            "avg_launch_us": round(ms / n_l * 1e3, 2),
+            "alg_gflop_per_launch": round(fl / n_l / 1e9, 3),
+            "all_gemm_ms_per_step": round(gemm_ms, 3), "all_gemm_tflop_per_step": round(all_fl / 1e12, 4),
+            "eager_step_ms": round(eager_ms, 3),
+            "eager_step_host_ms": round(r["eager_host_ms"], 3),
+            "dp_segments": {"ms": r["seg_ms"], "grad_bytes": r["seg_bytes"],
+                            "what": "eager step cut at the data-parallel buckets (forward + GPT-2 "
+                                    "backward, then one per mapper layer top first, then the mapper "
+                                    "input projection): HIP-event time and fp32 gradient bytes each "
+                                    "segment finalises (DESIGN.md §8(e) overlap arithmetic)"},
+            "gpt2_block": dict(r["block"], peak=BF16_PEAK_TFLOPS, unit="TFLOP/s",
+                               what="the 12 GPT-2 blocks' GEMMs (fwd + dX) and attention (fwd + bwd) of "
+                                    "one step: summed algorithmic FLOPs (live rows) / summed in-replay "
+                                    "kernel time (timing)"),
+            "timing": ("graph replay by difference: median replay of the step graph minus that of the "
+                       "same graph captured without the dominant instantiation's launches (and, for "
+                       "gpt2_block, without the block region's GEMM + attention launches), HIP events "
+                       "between replays (replay_roofline). The eager pass (HIP events around every "
+                       "launch, eager_roofline) picks the dominant kernel and prices the per-shape table"
+                       if r["replay_roofline"] and "dom_ms" in r["replay_roofline"] else
+                       "HIP events around every GEMM launch of one eager step on its launch stream (the "
+                       "replay pass was unavailable: replay_roofline)"),
+            "eager_roofline": {k: (round(v, 4) if isinstance(v, float) else v)
+                               for k, v in r["eager_roofline"].items()},
+            "replay_roofline": ({k: (round(v, 4) if isinstance(v, float) else v)
+                                 for k, v in r["replay_roofline"].items()}
+                                if r["replay_roofline"] else None)}
+
+
+DUMP_SAMPLE = 1 << 22  # elements kept of each flat buffer (16 MB as fp32; the buffers hold the mapper's ~61 M values)
+
+
+def dump_outputs(path, trainer):
+    """--dump-outputs: what the last timed step left for its caller, as float32 .npy files under `path`: loss (the
+    step's mean CE), params (the trained fp32 masters after its AdamW update) and grads (the gradients it applied,
+    as the optimizer left them). The two flat buffers are sampled at DUMP_SAMPLE fixed, seeded positions (all of
+    them when smaller), so two builds run with the same arguments are compared element for element."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    flat = trainer.flat
+    n = int(flat.n)
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20)).sort().values
+    else:
+        idx = torch.arange(n)
+    idx = idx.to(flat.flat.device)
+    out = {"loss": trainer.last_loss.reshape(-1), "params": flat.flat[idx], "grads": flat.flat_grad[idx]}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 EDIM = {"small": 512, "medium": 768, "large": 1024}  # image-embedding width per config (CLIP-B/32, CLIP-L/14, DINOv3-L)
 
 
@@ -701,7 +774,17 @@ def main():
     ap.add_argument("--sweep", default=None,
                     help="comma-separated extra per-GPU batches for the batch sweep (default: 8,32,256,512 for small)")
     ap.add_argument("--no-unfrozen", action="store_true", help="skip the freeze_gpt_weights=False line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, trained parameters, "
+                         "gradients; float32, seeded sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: GEMM roofline, decode rates, "
+                         "preprocessing / extraction, fp32 parity mode, padded / unfrozen steps, batch sweep, CPU "
+                         "baseline (each can be switched off with its --no-... option)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_decode = args.no_cpu_baseline = args.no_unfrozen = True
+        args.sweep = ""
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -741,11 +824,16 @@ def main():
     trainer.gws.live_rows_hint = token_rows if packed else None
     trainer.gws.seq_sq_hint = live_rows(labels, trainer.P, squares=True) if packed else None
     use_graph = not args.no_graph
-    # timed region + the kernel roofline pass (every GEMM launch of one eager step, timed with HIP events)
-    r = train_rate(trainer, B, args.steps, args.warmup, use_graph, world, dev, detail=True)
+    # timed region, its outputs, then (--full) the kernel roofline pass (every GEMM launch of one eager step, timed
+    # with HIP events)
+    r = timed_steps(trainer, B, args.steps, args.warmup, use_graph, world, dev)
     el, loss, imgs_per_s = r["el"], r["loss"], r["images_per_s"]
-    dom, n_l, fl, ms, achieved = r["dom"], r["n_l"], r["fl"], r["ms"], r["achieved"]
-    gemm_ms, all_fl, eager_ms = r["gemm_ms"], r["all_fl"], r["eager_ms"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)
+    dom = None
+    if args.full:
+        r.update(gemm_roofline(trainer, use_graph, detail=True))
+        dom = r["dom"]
 
     # -- greedy decode throughput ------------------------------------------------------------------------------
     Bd = args.decode_batch
@@ -761,7 +849,7 @@ def main():
         cb, dtb, ndb, lb = greedy_rate(model, 4 * Bd, dev, world)
         big = {"batch_per_gpu": 4 * Bd, "captions_per_s": round(cb, 1), "ms_per_batch": round(dtb / ndb * 1e3, 3)}
     # the committed PMC pass measured the configs[1] step: its per-launch bytes do not describe other configs
-    traffic, traffic_src = pmc_traffic(dom) if args.config == "small" else (None, None)
+    traffic, traffic_src = pmc_traffic(dom) if args.full and args.config == "small" else (None, None)
     prep = None if args.no_decode else preprocess_rate(dev)
     extract = extraction_child() if (not args.no_decode and args.config == "small" and rank == 0) else None
     parity = parity_mode_rate(B, dev) if (not args.no_decode and args.config == "small" and world == 1) else None
@@ -832,37 +920,7 @@ def main():
             "train_unfrozen": unfrozen,
             "data_parallel": dp,
             "batch_sweep": sweep,
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 1),
-                         "peak": kernel_peak(dom), "unit": "TFLOP/s", "frac": round(achieved / kernel_peak(dom), 4),
-                         "traffic": traffic, "traffic_unit": "bytes/launch (HBM, rocprofv3 PMC: 2 x FETCH_SIZE + WRITE_SIZE)",
-                         "traffic_source": traffic_src, "launches_per_step": n_l,
-                         "avg_launch_us": round(ms / n_l * 1e3, 2),
-                         "alg_gflop_per_launch": round(fl / n_l / 1e9, 3),
-                         "all_gemm_ms_per_step": round(gemm_ms, 3), "all_gemm_tflop_per_step": round(all_fl / 1e12, 4),
-                         "eager_step_ms": round(eager_ms, 3),
-                         "eager_step_host_ms": round(r["eager_host_ms"], 3),
-                         "dp_segments": {"ms": r["seg_ms"], "grad_bytes": r["seg_bytes"],
-                                         "what": "eager step cut at the data-parallel buckets (forward + GPT-2 "
-                                                 "backward, then one per mapper layer top first, then the mapper "
-                                                 "input projection): HIP-event time and fp32 gradient bytes each "
-                                                 "segment finalises (DESIGN.md §8(e) overlap arithmetic)"},
-                         "gpt2_block": dict(r["block"], peak=BF16_PEAK_TFLOPS, unit="TFLOP/s",
-                                            what="the 12 GPT-2 blocks' GEMMs (fwd + dX) and attention (fwd + bwd) of "
-                                                 "one step: summed algorithmic FLOPs (live rows) / summed in-replay "
-                                                 "kernel time (timing)"),
-                         "timing": ("graph replay by difference: median replay of the step graph minus that of the "
-                                    "same graph captured without the dominant instantiation's launches (and, for "
-                                    "gpt2_block, without the block region's GEMM + attention launches), HIP events "
-                                    "between replays (replay_roofline). The eager pass (HIP events around every "
-                                    "launch, eager_roofline) picks the dominant kernel and prices the per-shape table"
-                                    if r["replay_roofline"] and "dom_ms" in r["replay_roofline"] else
-                                    "HIP events around every GEMM launch of one eager step on its launch stream (the "
-                                    "replay pass was unavailable: replay_roofline)"),
-                         "eager_roofline": {k: (round(v, 4) if isinstance(v, float) else v)
-                                            for k, v in r["eager_roofline"].items()},
-                         "replay_roofline": ({k: (round(v, 4) if isinstance(v, float) else v)
-                                              for k, v in r["replay_roofline"].items()}
-                                             if r["replay_roofline"] else None)},
+            "roofline": roofline_fields(r, traffic, traffic_src) if args.full else None,
         }
         if not args.no_cpu_baseline and world == 1 and args.config == "small":
             res["cpu_baseline"] = cpu_baseline()

@@ -8,5 +8,5 @@ rc=$?; grep -E "FAIL|Error|passed|failed" $O/pytest.log | tail -6; [ $rc -eq 0 ]
 SHAPES=none timeout -k 10 300 python -u tools/gemm_tiles_ab.py > $O/kout_sweep.txt 2>&1 || { tail -5 $O/kout_sweep.txt; exit 1; }
 grep -v amdgpu.ids $O/kout_sweep.txt
 bash tools/pmc_lds.sh klds/lds || exit 1
-timeout -k 10 300 python -u bench.py --no-decode --no-cpu-baseline --sweep "" --no-unfrozen > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --no-decode --no-cpu-baseline --sweep "" --no-unfrozen > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
 tail -1 $O/bench.json | cut -c1-300

@@ -4,7 +4,7 @@ set -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd); O=$R/gpurun_out/varab; mkdir -p $O; cd $R
 run() {
   local tag=$1; shift
-  env ICAP_GEMM_DETAIL=$O/detail_$tag.txt "$@" timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-decode --sweep "" > $O/b_$tag.json 2> $O/b_$tag.err || return 1
+  env ICAP_GEMM_DETAIL=$O/detail_$tag.txt "$@" timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-decode --sweep "" > $O/b_$tag.json 2> $O/b_$tag.err || return 1
   python -c "import json; d=json.loads(open('$O/b_$tag.json').read().strip().splitlines()[-1]); print('$tag', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['all_gemm_ms_per_step'])"
 }
 run base ICAP_X=0 || exit 1

@@ -12,11 +12,11 @@ elif [ "$2" != "skip-tests" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1
   rc=$?; grep -E "FAIL|Error|passed|failed" $O/pytest.log | tail -6; [ $rc -eq 0 ] || exit $rc
 fi
-ICAP_GEMM_DETAIL=$O/gemm_detail.txt timeout -k 10 900 python -u bench.py > $O/bench.json 2> $O/bench.err
+ICAP_GEMM_DETAIL=$O/gemm_detail.txt timeout -k 10 900 python -u bench.py --full > $O/bench.json 2> $O/bench.err
 rc=$?; tail -1 $O/bench.json | cut -c1-400; [ $rc -eq 0 ] || { tail -5 $O/bench.err; exit $rc; }
 [ "$3" = "bench-only" ] && exit 0
 cd /tmp; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/p -o run -- python3 $R/bench.py --steps 8 --warmup 3 --no-decode --no-cpu-baseline --sweep "" > $O/prof_bench.json 2> $O/prof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/p -o run -- python3 $R/bench.py --full --steps 8 --warmup 3 --no-decode --no-cpu-baseline --sweep "" > $O/prof_bench.json 2> $O/prof.err
 rc=$?; [ $rc -eq 0 ] || { tail -5 $O/prof.err; exit $rc; }
 cd $R && python tools/kstats.py $O/p/run_results.db "the 8 timed train steps of 'bench.py --steps 8 --warmup 3 --no-decode --sweep \"\"' (packed B = 128, graph replay): kernels between the end of the 3rd and the 11th optimizer launch" --window adam_update_kernel 3 8 > $O/kstats.txt && head -16 $O/kstats.txt | cut -c1-150
 python tools/kstats.py $O/p/run_results.db "whole 'bench.py --steps 8 --warmup 3 --no-decode --sweep \"\"' run: model build (one-time: the fp32 GEMMs are the LayerNorm folds of the frozen weights), then the packed train step x 12 (3 warm-up + 8 timed + 1 eager roofline pass)" > $O/kstats_run.txt

@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/${1:-pmc_traffic}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 2 --warmup 1 --no-graph --no-decode --no-cpu-baseline"
+B="$R/bench.py --full --steps 2 --warmup 1 --no-graph --no-decode --no-cpu-baseline"
 timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE -d $O/f -o p -- python3 $B > $O/f.log 2>&1 || { tail -5 $O/f.log; exit 1; }
 timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE -d $O/w -o p -- python3 $B > $O/w.log 2>&1 || { tail -5 $O/w.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE -d $O/cf -o p -- python3 $R/tools/ab/copy_probe.py > $O/cf.log 2>&1 || exit 1

@@ -15,5 +15,5 @@ for v in product hs1 hs2 hs3 hs4; do
   ICAP_LIB=$L timeout -k 10 300 python -u tools/ab/ln_race_probe.py 2>&1 | grep -v amdgpu.ids | grep -v "fit:" >> $O/matrix.txt || { cat $O/matrix.txt; exit 1; }
 done
 cat $O/matrix.txt
-timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); r=d['roofline']; print(d['value'], r['frac'], r['gpt2_block'], r['replay_roofline'], r['eager_roofline'])"
