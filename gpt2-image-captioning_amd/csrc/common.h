@@ -7,38 +7,13 @@
 
 #include <hip/hip_runtime.h>
 
-// Diagnostic build only (make stamps: -DICAP_STAMPS): A/B overrides of the kernel choice read from the process
-// environment (tools/ab). The product library reads no environment variable: in it every choice is a function of
-// the call's arguments and diag_env returns its default at compile time.
-#ifdef ICAP_STAMPS
-#include <cstdlib>
-static inline int diag_env(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-#else
-static constexpr int diag_env(const char*, int dflt) { return dflt; }
-#endif
-#include <stdint.h>
-#include <string>
-
-#include "icap.h"
+#include "host_common.h"
 
 namespace icap {
 
 typedef uint16_t bf16_t;
 
-// ---- error reporting (thread-local, C-ABI icap_last_error) -------------------
-void set_error(const std::string& msg);
 int check_launch(const char* what);
-
-#define ICAP_REQUIRE(cond, msg)                 \
-  do {                                          \
-    if (!(cond)) {                              \
-      ::icap::set_error(std::string(msg));      \
-      return ICAP_ERR_ARG;                      \
-    }                                           \
-  } while (0)
 
 // ---- bf16 <-> f32 ------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t v) {
@@ -132,12 +107,6 @@ __device__ __forceinline__ uint64_t eff_seed(uint64_t seed, const uint64_t* ptr)
 // returns 0 or 1/(1-p)
 __device__ __forceinline__ float drop_scale(uint64_t seed, uint64_t idx, uint32_t thresh, float inv_keep) {
   return hash32(seed, idx) >= thresh ? inv_keep : 0.f;
-}
-inline uint32_t drop_threshold(float p) {
-  double t = (double)p * 4294967296.0;
-  if (t >= 4294967295.0) t = 4294967295.0;
-  if (t < 0) t = 0;
-  return (uint32_t)t;
 }
 
 // ---- activations -------------------------------------------------------------

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "common.h"
+#include "gemm_consts.h"
 
 #include <type_traits>
 
@@ -47,7 +48,7 @@ __host__ __device__ __forceinline__ int64_t mx_scale_off(int64_t R, int64_t row,
   return ((s * rg + (row >> 6)) * 16 + (row & 15)) * 16 + ((row >> 4) & 3) * 4 + (kblock & 3);
 }
 
-constexpr int GBM = 128, GBN = 128, GROWB = 128, GNT = 256;  // default 128x128 tile, 128-byte LDS rows
+constexpr int GROWB = 128;                         // 128-byte LDS rows (tile sizes: gemm_consts.h)
 constexpr uint32_t OOB = 0x80000000u;              // buffer offset beyond any num_records -> loads 0
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {
@@ -178,11 +179,10 @@ __device__ __forceinline__ void unpack_bf16(const uint4 w, float v[8]) {
 // NONE), ACT_ANY the runtime dispatch below, ACT_FWD + a forward activation a only, ACT_BWD + a backward dact a only:
 // the specialised forms compile a single straight run (no dispatch, none of the other activations' code, fewer live
 // registers in the epilogue); the arithmetic per element is act_fwd / act_bwd in every form (bitwise the same).
-constexpr int ACT_OFF = 0, ACT_ANY = 1, ACT_FWD = 16, ACT_BWD = 32;
+// (the values: gemm_consts.h)
 // LayerNorm statistics hand-off of the tile kernels (icap_gemm_args.ln_stats_out / ln_stats_in), or-ed into the
 // kernel's ACT template int above its activation kind: ACT_LNS = the producer writes (mean, M2) per row and 32-column
 // group of C; ACT_LNF = the consumer folds the LayerNorm of its A operand into its epilogue.
-constexpr int ACT_LNS = 256, ACT_LNF = 512;
 template <int W, int ACT = ACT_ANY>
 __device__ __forceinline__ void epi_bwd_math(const icap_gemm_args& p, float x[W], const float a[W], uint64_t seed,
                                              uint64_t didx, uint32_t drop_thresh, float inv_keep) {

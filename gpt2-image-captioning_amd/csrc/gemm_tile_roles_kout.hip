@@ -1,5 +1,5 @@
 #include "gemm_tile.h"
-#include "gemm_plan.h"
+#include "gemm_launch.h"
 
 namespace icap {
 
@@ -7,10 +7,11 @@ namespace icap {
 // the split-role ring of gemm_tile.h: 4 MFMA waves of 64 x 64 reading ds_read_b64_tr_b16 fragments from the T10 (b)
 // images + 4 LDS-DMA waves, 4 stages of 32 KiB, one block per CU walking tiles x splits; splits go through the slabs
 // and the reduce pass.
-void launch_tile_roles_kout(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
+int launch_tile_roles_kout(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
   ICAP_TILE_PRELUDE;
 #define ICAP_GKK(TC, KIND) \
   hipLaunchKernelGGL((gemm_kernel<bf16_t, TC, 4, 1, 2, 2, 4, 4, true, KIND, true>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep)
+  if (pl.actk != ACT_OFF && pl.actk != ACT_ANY) return gemm_no_instantiation(pl);
   if (p.c_dtype != ICAP_BF16) {
     if (pl.actk == ACT_OFF) ICAP_GKK(float, ACT_OFF);
     else ICAP_GKK(float, ACT_ANY);
@@ -19,6 +20,7 @@ void launch_tile_roles_kout(const GemmPlan& pl, const icap_gemm_args& p, int nks
     else ICAP_GKK(bf16_t, ACT_ANY);
   }
 #undef ICAP_GKK
+  return ICAP_OK;
 }
 
 // A group of K-outer products in ONE launch (icap_gemm_group, round 6): every block walks the concatenated tile list of

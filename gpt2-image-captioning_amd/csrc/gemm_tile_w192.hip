@@ -1,5 +1,5 @@
 #include "gemm_tile.h"
-#include "gemm_plan.h"
+#include "gemm_launch.h"
 
 namespace icap {
 
@@ -11,26 +11,29 @@ namespace icap {
 // Variant 25: the same tiles on the LDS-DMA ring (gemm_tile.h NST 4: three stages in flight, one
 // block per CU) for long K. (Round 5 also measured a fragment prefetch across the ring's stages and a register-staged
 // double buffer on these tiles — bitwise equal, neither faster: profiles/r05_w192_ab.txt; removed.)
-void launch_tile_w192(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
+int launch_tile_w192(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
   ICAP_TILE_PRELUDE;
 #define ICAP_GKW(TC, KIND)                                                                                                 \
   do {                                                                                                                     \
-    if (pl.variant == 25)                                                                                                  \
+    if (pl.variant == V_W192_RING)                                                                                         \
       hipLaunchKernelGGL((gemm_kernel<bf16_t, TC, 4, 1, 4, 1, 3, 4, false, KIND>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep); \
     else                                                                                                                   \
       hipLaunchKernelGGL((gemm_kernel<bf16_t, TC, 2, 2, 4, 1, 3, 4, false, KIND>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep); \
   } while (0)
   if (p.c_dtype != ICAP_BF16) {
     if (pl.actk == ACT_OFF) ICAP_GKW(float, ACT_OFF);
-    else ICAP_GKW(float, ACT_ANY);
-    return;
+    else if (pl.actk == ACT_ANY) ICAP_GKW(float, ACT_ANY);
+    else return gemm_no_instantiation(pl);
+    return ICAP_OK;
   }
   switch (pl.actk) {
     case ACT_OFF: ICAP_GKW(bf16_t, ACT_OFF); break;
     case ACT_LNS + ACT_OFF: ICAP_GKW(bf16_t, ACT_LNS + ACT_OFF); break;
-    default: ICAP_GKW(bf16_t, ACT_ANY); break;
+    case ACT_ANY: ICAP_GKW(bf16_t, ACT_ANY); break;
+    default: return gemm_no_instantiation(pl);
   }
 #undef ICAP_GKW
+  return ICAP_OK;
 }
 
 }  // namespace icap

@@ -283,7 +283,7 @@ def gemm_group(items) -> None:
 
 
 def ln_fold_ok(D: int) -> bool:
-    """The LayerNorm-statistics hand-off's shape rule (csrc/gemm.hip gemm_plan): the producer stores (mean, M2) per
+    """The LayerNorm-statistics hand-off's shape rule (csrc/gemm_plan.cpp): the producer stores (mean, M2) per
     32-column group (N % 32 == 0) and the consumer tile GEMM combines them in its prologue, K % 128 == 0 and
     K <= 1280. A model whose width breaks it (e.g. GPT-2 XL's 1600, or 192) keeps the standalone LayerNorm launches."""
     return D % 128 == 0 and D <= 1280

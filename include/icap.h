@@ -124,6 +124,8 @@ typedef struct {
   /*     LayerNorm hand-off) — same use; 11 = the K-outer split-role kernel (variant 31, 128 x 128 tiles) for bf16 */
   /*     trans_ab launches, K split over slabs by its own rule unless split_k is given — same use; 12 = the     */
   /*     split-role ring on 160 x 128 tiles (variant 32, no LayerNorm consumer) — same use.                     */
+  /*     Path 11 needs K > 0 (ICAP_ERR_ARG otherwise), as do paths 8 / 9 / 12 with split_k > 1. Path 11 caps a  */
+  /*     caller's split_k at 8 and lowers it until every split has at least 4 K stages of 64.                   */
   int32_t path;
   /* in_dtype == ICAP_FP8_MX: the E8M0 block scales of A (M rows) and B (N rows), K % 128 == 0, lda / ldb      */
   /* multiples of 16, 16-byte aligned. For a 128-element K stage s and 64-row group g, 256 bytes at offset      */

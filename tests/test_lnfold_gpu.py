@@ -117,7 +117,7 @@ def test_ln_stats_producer(dev, M, live, N, K, form):
     ops.gemm(A, B, C, ln_stats_out=st, **kw)
     C2 = torch.zeros_like(C)
     # the same product without the statistics: identical C. (300 rows: a plain launch of this shape splits K over
-    # slabs + a reduce pass; with ln_stats it runs unsplit — gemm.hip — so it is compared with the unsplit product)
+    # slabs + a reduce pass; with ln_stats it runs unsplit — gemm_plan.cpp — so it is compared with the unsplit product)
     ops.gemm(A, B, C2, **(dict(kw, split_k=1) if M == 300 else kw))
     torch.cuda.synchronize()
     rows = live or M

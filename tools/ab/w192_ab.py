@@ -5,7 +5,7 @@ at capture time): auto = the automatic plan; p7 = path 7 (natural k order: varia
 4-stage ring variant 25 past that); p7r3 / p7n2 = path 7 with the 3-stage ring / the double-buffered loop for long
 K (ICAP_W192R = 3 / 2; forms removed after round 5's third pass: p7r5 = fragment prefetch, p7rs = register staging);
 p7s2 / p7s3 = path 7 with K split 2 / 3 ways and combined inside the launch (ICAP_W192S); w192s = the automatic plan
-forced to the 192-row tiles with its K-skew (ICAP_W192 = 1). '!' = not allclose to auto; '#' = not bitwise equal to p7."""
+forced to the 192-row tiles with its K-skew. '!' = not allclose to auto; '#' = not bitwise equal to p7."""
 import os
 import sys
 
