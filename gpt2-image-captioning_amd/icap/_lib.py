@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("ICAP_LIB") or os.path.join(_HERE, "libicap_hip.so")
 
 F32, BF16, FP8_MX = 0, 1, 2
 ACT_NONE, ACT_GELU_NEW, ACT_RELU, ACT_QUICK_GELU, ACT_TANH, ACT_GELU_ERF = 0, 1, 2, 3, 4, 5
+AGG_MEAN, AGG_MAX, AGG_SUM_NORM = 0, 1, 2
 
 vp = C.c_void_p
 i32, i64, u64, f32, sz = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
@@ -167,6 +168,11 @@ SIGNATURES = {
     "icap_greedy_next": (C.c_int, [i32, i32, i64, vp, i64, i64, vp, vp, vp, i64, i32, vp, vp, i32, i32, vp, vp]),
     "icap_add_position": (C.c_int, [i32, i32, i32, i32, vp, i64, i64, vp, i32, vp, vp]),
     "icap_clip_preprocess": (C.c_int, [i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "icap_topk_rows_slice": (i32, []),
+    "icap_topk_rows_workspace_bytes": (sz, [i64, i64, i32]),
+    "icap_topk_rows": (C.c_int, [i64, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+    "icap_retrieval_aggregate": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, i64,
+                                           vp, vp, vp, i64, vp]),
 }
 
 _lib = None

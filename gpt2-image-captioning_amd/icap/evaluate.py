@@ -17,7 +17,8 @@ import torch
 
 
 def generate_predictions(model, dataset, batch_size: int = 128, max_length: int = 50, temperature: float = 0.0,
-                         top_p: float = 0.9, device=None):
+                         top_p: float = 0.9, device=None, rat=None):
+    """rat: (db_store, top_k, top_i) for a RetrievalAugmentedTransformer (src/eval.py:281-289)."""
     device = device or model.device
     seen, idx = set(), []
     for i in range(len(dataset)):  # one caption per image (eval.py:219-224)
@@ -29,7 +30,11 @@ def generate_predictions(model, dataset, batch_size: int = 128, max_length: int 
     for s in range(0, len(idx), batch_size):
         items = [dataset[i] for i in idx[s:s + batch_size]]
         emb = torch.stack([it["image_embedding"] for it in items]).to(device)
-        ids = model.generate(emb, max_length=max_length, temperature=temperature, top_p=top_p)
+        if rat is None:
+            ids = model.generate(emb, max_length=max_length, temperature=temperature, top_p=top_p)
+        else:
+            ids = model.generate(db_store=rat[0], top_k=rat[1], top_i=rat[2], image_embeddings=emb,
+                                 max_length=max_length, temperature=temperature, top_p=top_p)
         if hasattr(model.tokenizer, "batch_decode"):
             texts = model.tokenizer.batch_decode(ids.cpu(), skip_special_tokens=True)
         else:
@@ -89,6 +94,31 @@ def evaluate_epoch(model, dataset, annotations_path, epoch, split_name, batch_si
     with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_predictions.json"), "w") as f:
         json.dump(preds, f, indent=2)
     with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_metrics.json"), "w") as f:
+        json.dump({"epoch": epoch, "split": split_name, "num_images": len(preds), **m}, f, indent=2)
+    return m
+
+
+def generate_and_evaluate_rat(model, db_store, top_k: int, top_i: int, dataset, annotations_path, batch_size: int = 32,
+                              num_workers: int = 4, max_length: int = 50, temperature: float = 1.0,
+                              top_p: float = 0.9, device=None):
+    """src/eval.py:232-308: (predictions, metrics dict) of a RetrievalAugmentedTransformer over `db_store`."""
+    model.eval()
+    preds = generate_predictions(model, dataset, batch_size, max_length, temperature, top_p, device,
+                                 rat=(db_store, top_k, top_i))
+    return preds, (compute_caption_metrics(preds, annotations_path) if annotations_path else {})
+
+
+def evaluate_rat_epoch(model, db_store, top_k: int, top_i: int, dataset, annotations_path, epoch, split_name,
+                       batch_size: int = 32, num_workers: int = 4, max_length: int = 50, temperature: float = 1.0,
+                       top_p: float = 0.9, device=None, output_dir: str = "eval_results") -> Dict[str, Any]:
+    """src/eval.py:391-476: evaluate_epoch for the retrieval-augmented model; the files carry the reference's
+    `_rat` suffix (`epoch_{epoch}_{split}_predictions_rat.json`, `epoch_{epoch}_{split}_metrics_rat.json`)."""
+    os.makedirs(output_dir, exist_ok=True)
+    preds, m = generate_and_evaluate_rat(model, db_store, top_k, top_i, dataset, annotations_path, batch_size,
+                                         num_workers, max_length, temperature, top_p, device)
+    with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_predictions_rat.json"), "w") as f:
+        json.dump(preds, f, indent=2)
+    with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_metrics_rat.json"), "w") as f:
         json.dump({"epoch": epoch, "split": split_name, "num_images": len(preds), **m}, f, indent=2)
     return m
 

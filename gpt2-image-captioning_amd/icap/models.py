@@ -19,9 +19,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib as L
 from . import ops
 from .gpt2 import GPT2Config, GPT2LMHeadModel
 from .mapper import DWHelper, MLPMapperCore, MLPMappingNetwork, TransformerMapperCore, TransformerMappingNetwork
+from .retrieval import AGG_CODES, DeviceRetrievalStore, check_limits
 from .weights import FlatParams, named_trainable
 
 Tensor = torch.Tensor
@@ -260,6 +262,93 @@ class ImageCaptioningModel(nn.Module):
             raise ValueError(f"Missing keys found in the checkpoint that are not from frozen GPT weights: {non_gpt}")
         if not self.freeze_gpt_weights:
             self.gpt.invalidate_core()
+
+
+class RetrievalAggregator(nn.Module):
+    """src/models.py:550-625: query + pool(retrieved caption embeddings). "mean", "max" and "sum_norm" have no
+    parameters and run in icap_retrieval_aggregate. "attention" has trained parameters whose gradient the mapper
+    backward does not produce yet (retrieval follow-ups)."""
+
+    def __init__(self, embed_dim: int, aggregation_type: str = "mean"):
+        super().__init__()
+        if aggregation_type == "attention":
+            raise NotImplementedError('aggregation_type "attention" is not implemented: its attention_proj is '
+                                      "trained through d(image embedding), which the mapper backward does not "
+                                      'compute (use "mean", "max" or "sum_norm")')
+        self.aggregation_type = aggregation_type
+        self.embed_dim = embed_dim
+        self._tables = {}
+
+    def forward(self, query_embedding: Tensor, retrieved_embeddings: Tensor) -> Tensor:
+        """query [B, D] + aggregate(retrieved [B, top_k, D]) -> fp32 [B, D]. The kernel reads `retrieved` as a
+        caption table in which query b owns rows b * top_k ... (b + 1) * top_k - 1."""
+        if self.aggregation_type not in AGG_CODES:
+            raise ValueError(f"Unknown aggregation_type: {self.aggregation_type}")
+        B, top_k, D = retrieved_embeddings.shape
+        dev = retrieved_embeddings.device
+        L.require_device(dev)
+        key = (B, top_k, dev)
+        t = self._tables.get(key)
+        if t is None:
+            t = (torch.zeros((B, 1), dtype=torch.float32, device=dev),
+                 torch.arange(B, dtype=torch.int32, device=dev).view(B, 1),
+                 torch.arange(B + 1, dtype=torch.int32, device=dev) * top_k,
+                 torch.arange(B * top_k, dtype=torch.int32, device=dev))
+            self._tables[key] = t
+        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        ops.retrieval_aggregate(t[0], t[1], t[2], t[3], retrieved_embeddings.float().contiguous().view(B * top_k, D),
+                                query_embedding.to(dev).float().contiguous(), top_i=1, top_k=top_k,
+                                agg=AGG_CODES[self.aggregation_type], out=out)
+        return out
+
+
+class RetrievalAugmentedTransformer(ImageCaptioningModel):
+    """src/models.py:628-785 with the database on the device: the image embedding is replaced by
+    embedding + aggregate(caption embeddings of its top_i nearest database images) before the mapper. Checkpoint
+    keys are the base class's (the supported aggregators have no parameters). max_workers (the reference's
+    ObjectBox thread pool) is kept for the signature only."""
+
+    def __init__(self, embed_dim: int, max_workers: int = 4, aggregation_type: str = "mean", *args, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.max_workers = max_workers
+        self.aggregator = RetrievalAggregator(embed_dim, aggregation_type)
+
+    @staticmethod
+    def _store(db_store) -> DeviceRetrievalStore:
+        if not isinstance(db_store, DeviceRetrievalStore):
+            raise TypeError(f"db_store must be an icap.DeviceRetrievalStore, got {type(db_store).__name__}; convert "
+                            "a loaded FAISSStore with DeviceRetrievalStore.from_faiss_store(store, device)")
+        return db_store
+
+    def _retrieve_batch(self, db_store, image_embeddings: Tensor, top_i: int, top_k: int) -> Tensor:
+        """src/models.py:655-695 (the FAISS branch): fp32 [B, top_k, D], zero-padded."""
+        return self._store(db_store).retrieve(image_embeddings, top_i, top_k)
+
+    def augment(self, db_store, image_embeddings: Tensor, top_i: int, top_k: int,
+                out: Optional[Tensor] = None) -> Tensor:
+        """image_embeddings + aggregated retrieval as fp32 [B, D] (src/models.py:732-738): score GEMM, top-k and
+        aggregate on the current stream, no host synchronisation. The scratch is preallocated per batch size by the
+        store; with `out` given nothing is allocated, so the call can be captured in a graph."""
+        check_limits(top_i, top_k)
+        return self._store(db_store).augment(image_embeddings, top_i, top_k, self.aggregator.aggregation_type,
+                                             out=out)
+
+    def forward(self, db_store, top_i: int, top_k: int, caption_token_ids: Tensor, image_embeddings: Tensor,
+                attention_mask: Optional[Tensor] = None, labels: Optional[Tensor] = None):
+        aug = self.augment(db_store, image_embeddings, top_i, top_k)
+        return super().forward(caption_token_ids=caption_token_ids, image_embeddings=aug,
+                               attention_mask=attention_mask, labels=labels)
+
+    @torch.no_grad()
+    def generate(self, db_store, top_k: int, top_i: int, image_embeddings: Tensor, max_length: int = 50,
+                 temperature: float = 1.0, top_p: float = 0.9, **kwargs) -> Tensor:
+        """src/models.py:748-771 (top_k before top_i, as there); **kwargs: ImageCaptioningModel.generate's extras."""
+        aug = self.augment(db_store, image_embeddings, top_i, top_k)
+        return super().generate(aug, max_length, temperature, top_p, **kwargs)
+
+    def generate_captions(self, db_store, top_k: int, top_i: int, image_embeddings: Tensor, **kwargs) -> List[str]:
+        ids = self.generate(db_store, top_k, top_i, image_embeddings, **kwargs)
+        return self.tokenizer.batch_decode(ids, skip_special_tokens=True)
 
 
 def _embedding_grads(d_emb: Tensor, ids: Tensor, B: int, P: int, Lc: int, D: int, g, dwh: DWHelper) -> None:

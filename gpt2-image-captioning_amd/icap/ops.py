@@ -564,6 +564,63 @@ class BeamState:
         return self.out, self.out_len
 
 
+# ---------------------------------------------------------------------------------------------- retrieval
+def topk_rows_slice() -> int:
+    """Columns per block of icap_topk_rows' first launch (host-only query)."""
+    return int(L.load().icap_topk_rows_slice())
+
+
+def topk_rows_workspace(R: int, N: int, K: int) -> int:
+    n = int(L.load().icap_topk_rows_workspace_bytes(R, N, K))
+    if n == 0 and R:
+        raise L.IcapError(f"topk_rows: K = {K} must be in [1, 32]")
+    return n
+
+
+def topk_rows(scores: Tensor, K: int, top_val: Tensor, top_idx: Tensor, workspace: Tensor, *,
+              N: Optional[int] = None, col0: int = 0, merge: bool = False) -> None:
+    """top_val / top_idx [R, K] <- the K largest of each row of scores [R, N] (fp32; descending, ties to the lower
+    column; index -1 past N entries), indices offset by col0; merge: the lists already there are candidates too
+    (icap_topk_rows in include/icap.h). workspace: >= topk_rows_workspace(R, N, K) bytes."""
+    R = scores.shape[0]
+    N = scores.shape[1] if N is None else N
+    if scores.dtype != torch.float32 or top_val.dtype != torch.float32 or top_idx.dtype != torch.int32:
+        raise L.IcapError("topk_rows: fp32 scores / top_val and int32 top_idx")
+    if tuple(top_val.shape) != (R, K) or tuple(top_idx.shape) != (R, K) or not top_val.is_contiguous() \
+            or not top_idx.is_contiguous():
+        raise L.IcapError("topk_rows: top_val / top_idx must be contiguous [R, K]")
+    if workspace.numel() * workspace.element_size() < topk_rows_workspace(R, N, K):
+        raise L.IcapError("topk_rows: workspace too small")
+    call("icap_topk_rows", R, N, scores.data_ptr(), _ld(scores) if R else N, K, col0, 1 if merge else 0,
+         top_val.data_ptr(), top_idx.data_ptr(), workspace.data_ptr(), _stream())
+
+
+def retrieval_aggregate(top_val: Tensor, top_idx: Tensor, cap_ptr: Tensor, cap_rows: Tensor,
+                        caption_embeddings: Tensor, query: Optional[Tensor], *, top_i: int, top_k: int, agg: int,
+                        retrieved: Optional[Tensor] = None, cap_ids: Optional[Tensor] = None,
+                        out: Optional[Tensor] = None) -> None:
+    """The reference's candidate walk, caption gather, aggregation and query + aggregated for each row of
+    top_val / top_idx [B, K] (icap_retrieval_aggregate in include/icap.h). retrieved fp32 [B, top_k, D],
+    cap_ids int32 [B, top_k], out fp32 [B, D]: each optional."""
+    B, K = top_idx.shape
+    C_, D = caption_embeddings.shape
+    N = cap_ptr.numel() - 1
+    for t, dt in ((top_val, torch.float32), (top_idx, torch.int32), (cap_ptr, torch.int32), (cap_rows, torch.int32),
+                  (caption_embeddings, torch.float32), (query, torch.float32), (retrieved, torch.float32),
+                  (cap_ids, torch.int32), (out, torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise L.IcapError("retrieval_aggregate: operands must be contiguous fp32 / int32 tensors")
+    if retrieved is not None and tuple(retrieved.shape) != (B, top_k, D):
+        raise L.IcapError("retrieval_aggregate: retrieved must be [B, top_k, D]")
+    if cap_ids is not None and tuple(cap_ids.shape) != (B, top_k):
+        raise L.IcapError("retrieval_aggregate: cap_ids must be [B, top_k]")
+    if out is not None and (query is None or tuple(out.shape) != (B, D) or tuple(query.shape) != (B, D)):
+        raise L.IcapError("retrieval_aggregate: out and query must be [B, D]")
+    call("icap_retrieval_aggregate", B, D, K, top_i, top_k, agg, top_val.data_ptr(), top_idx.data_ptr(), N,
+         cap_ptr.data_ptr(), _p(cap_rows) if cap_rows.numel() else None, C_,
+         _p(caption_embeddings) if C_ else None, _p(query), D, _p(retrieved), _p(cap_ids), _p(out), D, _stream())
+
+
 def gpt2_embed(prefix: Optional[Tensor], prefix_bstride: int, wte: Tensor, wpe: Tensor, ids: Optional[Tensor],
                x: Tensor, *, B: int, P: int, L_: int, D: int, drop: Dropout = NO_DROP, seqs=None) -> Tensor:
     """seqs: (seq_off, seq_len) — write the live tokens of each sequence at its packed rows."""

@@ -1,4 +1,4 @@
-"""train() — drop-in for src/train.py:20-254 on the fused icap step (engine.CaptionTrainer).
+"""train() / train_rat() — drop-ins for src/train.py:20-254 / 257-483 on the fused icap step (engine.CaptionTrainer).
 
 Same signature, defaults, ValueError rule, checkpoint cadence and return dict. Differences
 by design: the step runs as one captured HIP graph (forward, backward, clip_grad_norm,
@@ -18,6 +18,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .engine import CaptionTrainer
+from .retrieval import check_limits
 
 
 def _collate(batch):
@@ -34,6 +35,40 @@ def train(train_dataset, model, batch_size: int, num_epochs: int, num_workers: i
           val_annotations_path: Optional[str] = None, eval_every_epoch: int = 1, eval_batch_size: Optional[int] = None,
           eval_max_length: int = 50, eval_temperature: float = 0.0, eval_top_p: float = 0.9, *, clip_model=None,
           use_graph: bool = True, log_every: int = 0, dropout: bool = True, seed: int = 0) -> dict[str, Any]:
+    return _fit(None, train_dataset, model, batch_size, num_epochs, num_workers, learning_rate, num_warmup_steps,
+                save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset, val_annotations_path,
+                eval_every_epoch, eval_batch_size, eval_max_length, eval_temperature, eval_top_p, clip_model,
+                use_graph, log_every, dropout, seed)
+
+
+def train_rat(train_dataset, model, db_store, top_k: int, top_i: int, batch_size: int, num_epochs: int,
+              num_workers: int = 4, learning_rate: float = 1e-4, num_warmup_steps: int = 0, save_every_epoch: int = 5,
+              device: Optional[torch.device] = None, outputs_dir: str = "checkpoints", grad_accum_steps: int = 1,
+              val_dataset=None, val_annotations_path: Optional[str] = None, eval_every_epoch: int = 1,
+              eval_batch_size: Optional[int] = None, eval_max_length: int = 50, eval_temperature: float = 0.0,
+              eval_top_p: float = 0.9, *, clip_model=None, use_graph: bool = True, log_every: int = 0,
+              dropout: bool = True, seed: int = 0) -> dict[str, Any]:
+    """src/train.py:257-483 for a RetrievalAugmentedTransformer: train() with one added step per batch. The batch's
+    image embeddings go to the device, model.augment (score GEMM, top-k, aggregate: no host synchronisation) replaces
+    them by embedding + aggregated retrieval, and the fused step runs on the result. The best model is saved as
+    best_rat_model_epoch_{e}.pt and validation goes through evaluate_rat_epoch. Under torch.distributed every rank
+    holds a full replica of db_store on its own device."""
+    if clip_model is not None:
+        raise ValueError("train_rat takes precomputed image embeddings: retrieval augments the embedding before the "
+                         "step, so clip_model (pixels inside the step's graph) is not supported")
+    model._store(db_store)
+    check_limits(top_i, top_k)
+    return _fit((db_store, top_k, top_i), train_dataset, model, batch_size, num_epochs, num_workers, learning_rate,
+                num_warmup_steps, save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset,
+                val_annotations_path, eval_every_epoch, eval_batch_size, eval_max_length, eval_temperature,
+                eval_top_p, None, use_graph, log_every, dropout, seed)
+
+
+def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learning_rate, num_warmup_steps,
+         save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset, val_annotations_path, eval_every_epoch,
+         eval_batch_size, eval_max_length, eval_temperature, eval_top_p, clip_model, use_graph, log_every, dropout,
+         seed) -> dict[str, Any]:
+    """The loop of train() and train_rat(); rat = (db_store, top_k, top_i) or None."""
     os.makedirs(outputs_dir, exist_ok=True)
     eval_dir = os.path.join(outputs_dir, "eval_results")
     os.makedirs(eval_dir, exist_ok=True)
@@ -65,6 +100,7 @@ def train(train_dataset, model, batch_size: int, num_epochs: int, num_workers: i
             trainers[key] = t
         return trainers[key]
 
+    aug_out: dict[int, torch.Tensor] = {}  # augmented embeddings per batch size (train_rat)
     epoch_loss_values: list[float] = []
     val_metrics_history: list[dict[str, Any]] = []
     best_val_cider, best_epoch = -1.0, 0
@@ -84,7 +120,13 @@ def train(train_dataset, model, batch_size: int, num_epochs: int, num_workers: i
             # device buffers asynchronously and reads the packed attention's short-sequence flag from the host
             # labels on the way (moving the labels to the device first turned that flag off for every batch:
             # ADVICE r05, engine.load_batch)
-            t.load_batch(ids, mask, labels, emb=batch["image_embedding"], pixels=pixels)
+            emb = batch["image_embedding"]
+            if rat is not None:  # src/train.py:365-373: retrieval on the device, into this batch size's buffer
+                B = ids.shape[0]
+                if B not in aug_out:
+                    aug_out[B] = torch.empty((B, emb.shape[1]), dtype=torch.float32, device=device)
+                emb = model.augment(rat[0], emb.to(device, non_blocking=True), rat[2], rat[1], out=aug_out[B])
+            t.load_batch(ids, mask, labels, emb=emb, pixels=pixels)
             # train.py:128-159: a cycle starts after each optimizer step; the step is taken every grad_accum_steps
             # batches and at the last batch of the epoch. The cycle's micro-batches accumulate into one shared
             # gradient buffer even when a short last batch runs on another trainer (its own batch shape).
@@ -107,13 +149,17 @@ def train(train_dataset, model, batch_size: int, num_epochs: int, num_workers: i
             path = os.path.join(outputs_dir, f"model_epoch_{epoch + 1}.pt")
             model.save_parameters(path)
         if val_dataset is not None and (epoch + 1) % eval_every_epoch == 0:
-            from .evaluate import evaluate_epoch
+            from .evaluate import evaluate_epoch, evaluate_rat_epoch
 
             # replicated weights: rank 0 decodes and writes the predictions file, then shares the metrics
             m = None
-            if is_main:
+            if is_main and rat is None:
                 m = evaluate_epoch(model, val_dataset, val_annotations_path, epoch + 1, "val", eval_batch_size,
                                    num_workers, eval_max_length, eval_temperature, eval_top_p, device, eval_dir)
+            elif is_main:
+                m = evaluate_rat_epoch(model, rat[0], rat[1], rat[2], val_dataset, val_annotations_path, epoch + 1,
+                                       "val", eval_batch_size, num_workers, eval_max_length, eval_temperature,
+                                       eval_top_p, device, eval_dir)
             if dist:
                 box = [m]
                 torch.distributed.broadcast_object_list(box, src=0)
@@ -123,7 +169,8 @@ def train(train_dataset, model, batch_size: int, num_epochs: int, num_workers: i
             if cider > best_val_cider:
                 best_val_cider, best_epoch = cider, epoch + 1
                 if is_main:
-                    model.save_parameters(os.path.join(outputs_dir, f"best_model_epoch_{best_epoch}.pt"))
+                    best = "best_model_epoch" if rat is None else "best_rat_model_epoch"  # src/train.py:445-447
+                    model.save_parameters(os.path.join(outputs_dir, f"{best}_{best_epoch}.pt"))
             model.train()
     if is_main and val_metrics_history:  # src/train.py:229-235 (the metric-curve PNG is out of scope)
         from .evaluate import save_eval_summary

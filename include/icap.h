@@ -533,6 +533,45 @@ int icap_clip_preprocess(int32_t n, const uint8_t* pixels, const int64_t* geo, i
                          int32_t max_tmp_rows, uint8_t* tmp, const float* mean, const float* stdv,
                          float* out, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Retrieval augmentation (src/models.py:550-785 over src/database/           */
+/* faiss_store.py): the database lives on the device. Per forward: scores     */
+/* S = Q . X^T through icap_gemm (fp32), icap_topk_rows, then                 */
+/* icap_retrieval_aggregate. Nothing here allocates or synchronises.          */
+/* ------------------------------------------------------------------------- */
+enum { ICAP_AGG_MEAN = 0, ICAP_AGG_MAX = 1, ICAP_AGG_SUM_NORM = 2 };
+/* The search of faiss_store.py:153 (IndexFlatIP.search(q, top_i + 10)) over a score matrix: for each of R rows  */
+/* of scores [R, N] (fp32, leading dimension ld) the K <= 32 largest values, descending, ties to the lower       */
+/* column, into top_val / top_idx [R, K]; stored indices are col0 + column. With N < K the tail is               */
+/* (-inf, index -1), as FAISS pads. Two launches: per (row, slice of icap_topk_rows_slice() columns) partial     */
+/* lists into `workspace` (icap_topk_rows_workspace_bytes(R, N, K), 4-byte aligned), then a merge per row.       */
+/* merge != 0: the lists already in top_val / top_idx are candidates too, so a caller that scores the database   */
+/* in column chunks folds chunk after chunk (col0 = the chunk's first column) into the same lists; the result    */
+/* is bitwise that of one call over all columns. col0 + N < 2^31.                                                */
+int32_t icap_topk_rows_slice(void);
+size_t icap_topk_rows_workspace_bytes(int64_t R, int64_t N, int32_t K);
+int icap_topk_rows(int64_t R, int64_t N, const float* scores, int64_t ld, int32_t K, int32_t col0, int32_t merge,
+                   float* top_val, int32_t* top_idx, void* workspace, void* stream);
+/* One block per query b over its row of top_val / top_idx [B, K] (image indices < N):                            */
+/*  1. walk the K candidates in order, skipping index -1 and any score that, as a double, is > 0.9999 (the        */
+/*     query's own image), until top_i images are kept (faiss_store.py:163-181 retrieve_images_by_vector_         */
+/*     similarity);                                                                                               */
+/*  2. concatenate the kept images' caption rows cap_rows[cap_ptr[n] .. cap_ptr[n+1]) in order, stopping after    */
+/*     the image that brings the list to top_k or more, and keep the first top_k (faiss_store.py:208-229          */
+/*     get_caption_embeddings);                                                                                   */
+/*  3. retrieved [B, top_k, D] (or NULL) = those rows of caption_embeddings [C, D], zero-padded (:221-246);       */
+/*     cap_ids [B, top_k] (or NULL) = the rows, padded with -1;                                                   */
+/*  4. aggregate over all top_k rows, pads included (src/models.py:589-606 RetrievalAggregator.forward):          */
+/*     ICAP_AGG_MEAN sum / top_k; ICAP_AGG_MAX elementwise max; ICAP_AGG_SUM_NORM rows x / max(|x|, 1e-12)        */
+/*     summed, then normalised the same way;                                                                      */
+/*  5. out [B, D] (ld ldo, or NULL) = query [B, D] (ld ldq) + aggregated (src/models.py:623).                     */
+/* All fp32. 1 <= top_i <= 22, 1 <= top_k <= 64, K <= 32, D % 4 == 0, float buffers 16-byte aligned.              */
+int icap_retrieval_aggregate(int32_t B, int32_t D, int32_t K, int32_t top_i, int32_t top_k, int32_t agg,
+                             const float* top_val, const int32_t* top_idx, int64_t N, const int32_t* cap_ptr,
+                             const int32_t* cap_rows, int64_t C, const float* caption_embeddings,
+                             const float* query, int64_t ldq, float* retrieved, int32_t* cap_ids, float* out,
+                             int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
