@@ -1032,9 +1032,11 @@ __global__ __launch_bounds__(1024) void greedy_next_kernel(int64_t V, const T* _
       // 16-byte loads, eight per thread in flight at once (a 50,304-logit row is one pass). Each thread visits its
       // logits in increasing index order, so a strict `>` keeps its first maximum (3 VALU ops per logit instead
       // of the NaN-aware 64-bit compare); a NaN anywhere in the row sends the block to the exact loop below.
+      // fi starts at the thread's first logit, so a thread whose logits are all -inf (which no `>` beats) still
+      // reports its first one: an all -inf row gives token 0, as torch.argmax does, not the first tail logit.
       const int64_t V8 = V >> 3;
       float fb = -INFINITY;
-      int fi = (int)V;
+      int fi = threadIdx.x < V8 ? 8 * (int)threadIdx.x : (int)V;
       bool nan = false;
       for (int64_t q0 = threadIdx.x; q0 < V8; q0 += 8 * NT) {
         uint4 w[8];
@@ -1140,7 +1142,7 @@ __global__ __launch_bounds__(256) void greedy_part_kernel(int64_t V, const T* __
     if (vec == 2) {  // c0 % 8 == 0 (chunk is a multiple of 8): 16-byte loads, first maximum per thread by strict >
       const int64_t q0b = c0 >> 3, q1 = c1 >> 3;
       float fb = -INFINITY;
-      int64_t fi = V;
+      int64_t fi = q0b + threadIdx.x < q1 ? 8 * (q0b + threadIdx.x) : V;  // (all -inf: the thread's first logit)
       bool nan = false;
       for (int64_t q = q0b + threadIdx.x; q < q1; q += NT) {
         const uint4 w = *reinterpret_cast<const uint4*>(row + 8 * q);

@@ -38,8 +38,10 @@ _orig_accesses = dryrun.accesses
 @pytest.fixture()
 def rec(monkeypatch):
     monkeypatch.setattr(dryrun, "accesses", _accesses)
+    # dry_run() itself swaps ops.call (icap.weights.ops is that module) and puts it back. Setting it again through
+    # monkeypatch would make monkeypatch's later undo reinstall the recorder for every test that follows.
+    assert icap.weights.ops is ops
     with dryrun.dry_run() as r:
-        monkeypatch.setattr(icap.weights.ops, "call", r)
         yield r
 
 
