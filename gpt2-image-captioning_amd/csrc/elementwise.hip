@@ -4,6 +4,9 @@
 
 #include <math.h>
 
+#include <algorithm>
+#include <vector>
+
 namespace icap {
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -640,6 +643,129 @@ __global__ __launch_bounds__(256) void adam_update_kernel(int64_t n, float* __re
       adam_one(p, G[i], m, v, clip, decay, w1, beta2, w2, step_size, bc2s, eps);
       P[i] = p; M1[i] = m; M2[i] = v;
       if (out16) out16[i] = f2bf(p);
+    }
+  }
+}
+
+// The same update with the transposed bf16 copies of some matrices written by the kernel that produces their values
+// (the trained mapper's [in, out] copies: a separate transpose launch re-read the 113 MB of bf16 the update had just
+// written). The flat range is cut into segments in offset order: a matrix item, walked as 64-row x 256-column tiles,
+// or the flat run between two items (biases, LayerNorm parameters, alignment gaps, everything past the last item),
+// walked in units of 4096 float4 groups. One block per tile / unit; per element the arithmetic is adam_one as in
+// adam_update_kernel, so p, m, v and bf16_out are bitwise what that kernel writes. A tile's bf16 values also go to
+// LDS ([row][col], row stride 258 halves: the column gathers below are conflict-free), and after a barrier 8
+// consecutive lanes write one column's 64 rows: 128 contiguous bytes of dst per column, 16 per lane.
+constexpr int ADAM_ITEMS = 32;
+constexpr int ADAM_SEGS = 2 * ADAM_ITEMS + 1;
+constexpr int ADAM_TR = 64, ADAM_TC = 256, ADAM_TLD = ADAM_TC + 2;
+constexpr int ADAM_UNIT4 = 4096;  // float4 groups per flat unit (= the elements of a tile / 4): 16 per thread
+struct AdamPlan {
+  int nseg;
+  int32_t off[ADAM_SEGS + 1];  // first block of each segment
+  int64_t start[ADAM_SEGS];    // first flat element (a multiple of 4)
+  int64_t rows[ADAM_SEGS];     // item: rows (a multiple of 64); 0: a flat run
+  int64_t cols[ADAM_SEGS];     // item: cols (a multiple of 8); flat run: its float4 groups
+  uint16_t* dst[ADAM_SEGS];
+  int64_t ldd[ADAM_SEGS];
+};
+
+// The fp32 masters and the two moments are read and written once per step and by nothing else before the next one:
+// non-temporal accesses (the gradients, bf16_out and the transposed copies keep the default policy: the norm pass
+// just read the first, the next step's GEMMs read the others). Measured: 356.0 -> 342.5 µs per launch at the
+// flagship shape (profiles/r07_adam_items_ab.txt), beyond the kernel's 6-8 µs min-max spread.
+typedef float adam_f4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 adam_ld4(const float* x, int64_t i4) {
+  const adam_f4_t t = __builtin_nontemporal_load(reinterpret_cast<const adam_f4_t*>(x) + i4);
+  return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ void adam_st4(float* x, int64_t i4, const float4& v) {
+  const adam_f4_t t = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(t, reinterpret_cast<adam_f4_t*>(x) + i4);
+}
+
+__global__ __launch_bounds__(256) void adam_update_items_kernel(int64_t n, float* __restrict__ P,
+                                                               const float* __restrict__ G, float* __restrict__ M1,
+                                                               float* __restrict__ M2, bf16_t* __restrict__ out16,
+                                                               const AdamState* __restrict__ st, float beta1,
+                                                               float beta2, float eps, AdamPlan pl) {
+  __shared__ __attribute__((aligned(16))) uint16_t tile[ADAM_TR * ADAM_TLD];
+  const float clip = st->clip, decay = st->decay, step_size = st->step_size, bc2s = st->bc2_sqrt;
+  const float w1 = 1.f - beta1, w2 = 1.f - beta2;
+  const int bid = blockIdx.x, tid = threadIdx.x;
+  int s = 0;
+  while (s + 1 < pl.nseg && bid >= pl.off[s + 1]) ++s;  // block-uniform
+  const int64_t u = bid - pl.off[s];
+  const int64_t base = pl.start[s], rows = pl.rows[s], cols = pl.cols[s];
+  int64_t r0 = 0, c0 = 0;
+  const int lane = tid & 63, w = tid >> 6;
+  if (rows) {
+    const int64_t tx = (cols + ADAM_TC - 1) / ADAM_TC;
+    const int64_t ty = u / tx;
+    r0 = ty * ADAM_TR;
+    c0 = (u - ty * tx) * ADAM_TC;
+  }
+#pragma unroll 1
+  for (int k0 = 0; k0 < 16; k0 += 4) {
+    int64_t i4[4];  // this thread's next 4 float4 groups (-1: none): all loads issued before the first update
+    float4 p[4], g[4], m[4], v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int k = k0 + q;
+      if (rows) {  // row w + 4k of the tile, columns c0 + 4 lane ..+3
+        const int64_t c = c0 + 4 * lane;
+        i4[q] = c < cols ? (base + (r0 + w + 4 * k) * cols + c) >> 2 : -1;
+      } else {
+        const int64_t j = u * ADAM_UNIT4 + k * 256 + tid;
+        i4[q] = j < cols ? (base >> 2) + j : -1;
+      }
+      if (i4[q] >= 0) {
+        p[q] = adam_ld4(P, i4[q]);
+        g[q] = reinterpret_cast<const float4*>(G)[i4[q]];
+        m[q] = adam_ld4(M1, i4[q]);
+        v[q] = adam_ld4(M2, i4[q]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (i4[q] < 0) continue;
+      adam_one(p[q].x, g[q].x, m[q].x, v[q].x, clip, decay, w1, beta2, w2, step_size, bc2s, eps);
+      adam_one(p[q].y, g[q].y, m[q].y, v[q].y, clip, decay, w1, beta2, w2, step_size, bc2s, eps);
+      adam_one(p[q].z, g[q].z, m[q].z, v[q].z, clip, decay, w1, beta2, w2, step_size, bc2s, eps);
+      adam_one(p[q].w, g[q].w, m[q].w, v[q].w, clip, decay, w1, beta2, w2, step_size, bc2s, eps);
+      adam_st4(P, i4[q], p[q]);
+      adam_st4(M1, i4[q], m[q]);
+      adam_st4(M2, i4[q], v[q]);
+      const uint2 o = make_uint2(f2bf2(p[q].x, p[q].y), f2bf2(p[q].z, p[q].w));  // io<bf16_t>::st4's rounding
+      *reinterpret_cast<uint2*>(out16 + 4 * i4[q]) = o;
+      if (rows) {
+        uint32_t* t = reinterpret_cast<uint32_t*>(&tile[(w + 4 * (k0 + q)) * ADAM_TLD + 4 * lane]);
+        t[0] = o.x;
+        t[1] = o.y;
+      }
+    }
+  }
+  if (rows) {  // block-uniform
+    __syncthreads();
+    uint16_t* dst = pl.dst[s];
+    const int64_t ldd = pl.ldd[s];
+#pragma unroll
+    for (int h = 0; h < 8; ++h) {
+      const int idx = tid + 256 * h;
+      const int rq = idx & 7, c = idx >> 3;
+      if (c0 + c >= cols) continue;
+      uint32_t x[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        x[e] = (uint32_t)tile[(8 * rq + 2 * e) * ADAM_TLD + c] | ((uint32_t)tile[(8 * rq + 2 * e + 1) * ADAM_TLD + c] << 16);
+      *reinterpret_cast<uint4*>(dst + (c0 + c) * ldd + r0 + 8 * rq) = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+  }
+  if (bid == 0) {  // the n % 4 tail lies past every item
+    for (int64_t i = (n & ~(int64_t)3) + tid; i < n; i += 256) {
+      float p = P[i], m = M1[i], v = M2[i];
+      adam_one(p, G[i], m, v, clip, decay, w1, beta2, w2, step_size, bc2s, eps);
+      P[i] = p; M1[i] = m; M2[i] = v;
+      out16[i] = f2bf(p);
     }
   }
 }
@@ -1551,6 +1677,61 @@ extern "C" int icap_adamw_step(const icap_adamw_args* a, void* workspace, void* 
                "icap_adamw_step: buffers must be 16-byte aligned");
   ICAP_REQUIRE(a->bf16_out == nullptr || (reinterpret_cast<uintptr_t>(a->bf16_out) & 7) == 0,
                "icap_adamw_step: bf16_out must be 8-byte aligned");
+  // the transposed copies: which items the update kernel writes itself (pl), which go to icap_transpose_batch (rest)
+  AdamPlan pl;
+  pl.nseg = 0;
+  pl.off[0] = 0;
+  std::vector<icap_transpose_item> rest_v;
+  ICAP_REQUIRE(a->n_items >= 0 && (a->n_items == 0 || (a->items && a->bf16_out)),
+               "icap_adamw_step: items need an item array and bf16_out");
+  if (a->n_items > 0) {
+    std::vector<icap_adamw_item> its(a->items, a->items + a->n_items);
+    std::sort(its.begin(), its.end(),
+              [](const icap_adamw_item& x, const icap_adamw_item& y) { return x.offset < y.offset; });
+    const bool out_ok = (reinterpret_cast<uintptr_t>(a->bf16_out) & 15) == 0;
+    int64_t cur = 0, total = 0;
+    int taken = 0;
+    auto flat_run = [&](int64_t lo, int64_t hi) {  // [lo, hi): lo % 4 == 0
+      const int64_t len4 = (hi - lo) >> 2;
+      if (len4 <= 0) return;
+      const int k = pl.nseg++;
+      pl.start[k] = lo; pl.rows[k] = 0; pl.cols[k] = len4; pl.dst[k] = nullptr; pl.ldd[k] = 0;
+      total += (len4 + ADAM_UNIT4 - 1) / ADAM_UNIT4;
+      pl.off[k + 1] = (int32_t)total;
+    };
+    int64_t prev_end = 0;
+    for (const icap_adamw_item& it : its) {
+      ICAP_REQUIRE(it.dst && it.offset >= 0 && it.rows >= 0 && it.cols >= 0 && it.ldd >= it.rows &&
+                       (it.cols == 0 || it.rows <= (a->n - it.offset) / it.cols) && it.offset <= a->n,
+                   "icap_adamw_step: item outside the flat buffer or ldd < rows");
+      ICAP_REQUIRE(it.offset >= prev_end, "icap_adamw_step: items overlap");
+      const int64_t end = it.offset + it.rows * it.cols;
+      prev_end = end;
+      if (it.rows == 0 || it.cols == 0) continue;
+      const bool tile = out_ok && taken < ADAM_ITEMS && it.offset % 8 == 0 && it.rows % ADAM_TR == 0 &&
+                        it.cols % 8 == 0 && it.ldd % 8 == 0 && (reinterpret_cast<uintptr_t>(it.dst) & 15) == 0;
+      if (!tile) {
+        rest_v.push_back(icap_transpose_item{static_cast<const uint16_t*>(a->bf16_out) + it.offset, it.cols, it.dst,
+                                             it.ldd, it.rows, it.cols});
+        continue;
+      }
+      flat_run(cur, it.offset);
+      const int k = pl.nseg++;
+      pl.start[k] = it.offset; pl.rows[k] = it.rows; pl.cols[k] = it.cols;
+      pl.dst[k] = static_cast<uint16_t*>(it.dst); pl.ldd[k] = it.ldd;
+      total += (it.rows / ADAM_TR) * ((it.cols + ADAM_TC - 1) / ADAM_TC);
+      ICAP_REQUIRE(total < (1ll << 31), "icap_adamw_step: too many tiles");
+      pl.off[k + 1] = (int32_t)total;
+      cur = end;
+      ++taken;
+    }
+    if (taken) {
+      flat_run(cur, a->n);
+      ICAP_REQUIRE(total < (1ll << 31), "icap_adamw_step: too many blocks");
+    }
+  }
+  const int32_t n_rest = (int32_t)rest_v.size();
+  const icap_transpose_item* rest = rest_v.data();
   if (a->n <= 0) return ICAP_OK;
   hipStream_t s = S_(stream);
   float* partial = reinterpret_cast<float*>(workspace);
@@ -1562,10 +1743,19 @@ extern "C" int icap_adamw_step(const icap_adamw_args* a, void* workspace, void* 
                      a->num_training_steps);
   rc = check_launch("icap_adamw_step(finalize)");
   if (rc) return rc;
-  hipLaunchKernelGGL(adam_update_kernel, dim3(nblk(a->n / 4 + 1, 256, 4096)), dim3(256), 0, s, a->n, a->params,
-                     a->grads, a->exp_avg, a->exp_avg_sq, (bf16_t*)a->bf16_out, (const AdamState*)a->state, a->beta1,
-                     a->beta2, a->eps);
-  return check_launch("icap_adamw_step(update)");
+  if (pl.nseg == 0) {
+    hipLaunchKernelGGL(adam_update_kernel, dim3(nblk(a->n / 4 + 1, 256, 4096)), dim3(256), 0, s, a->n, a->params,
+                       a->grads, a->exp_avg, a->exp_avg_sq, (bf16_t*)a->bf16_out, (const AdamState*)a->state,
+                       a->beta1, a->beta2, a->eps);
+    rc = check_launch("icap_adamw_step(update)");
+  } else {
+    hipLaunchKernelGGL(adam_update_items_kernel, dim3((unsigned)pl.off[pl.nseg]), dim3(256), 0, s, a->n, a->params,
+                       a->grads, a->exp_avg, a->exp_avg_sq, (bf16_t*)a->bf16_out, (const AdamState*)a->state,
+                       a->beta1, a->beta2, a->eps, pl);
+    rc = check_launch("icap_adamw_step(update + transposed copies)");
+  }
+  if (rc || n_rest == 0) return rc;
+  return icap_transpose_batch(n_rest, rest, stream);
 }
 
 extern "C" int icap_transpose(int32_t dtype, int64_t rows, int64_t cols, const void* src, int64_t lds, void* dst,

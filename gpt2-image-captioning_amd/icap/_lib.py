@@ -97,7 +97,12 @@ class AdamWArgs(C.Structure):
         ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32),
         ("max_norm", f32),
         ("num_warmup_steps", i64), ("num_training_steps", i64),
+        ("n_items", i32), ("items", vp),
     ]
+
+
+class AdamWItem(C.Structure):
+    _fields_ = [("offset", i64), ("rows", i64), ("cols", i64), ("dst", vp), ("ldd", i64)]
 
 
 class BeamArgs(C.Structure):

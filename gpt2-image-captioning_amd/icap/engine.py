@@ -27,6 +27,9 @@ SHORT_ONLY = True
 # micro-batch) instead of zeroing the flat gradient buffer and accumulating into it; False restores the zero_() +
 # accumulate form
 GRAD_OVERWRITE = True
+# the optimizer kernel writes the trained mapper's transposed bf16 weight copies itself (icap_adamw_args.items;
+# bitwise the stand-alone transposes); False restores the transpose launch after the update
+ADAM_TRANSPOSE = True
 
 Tensor = torch.Tensor
 
@@ -305,13 +308,30 @@ class CaptionTrainer:
             ops.convert(d_pre[:, : Pm * D], self.mws.dout.view(B, Sm * D)[:, Hl * D:])
         return d_emb
 
+    def _adam_items(self):
+        """The trained mapper's (flat offset, rows, cols, transposed copy) for ops.adamw_step(items=...): its bf16
+        weights are views of the flat bf16 mirror the optimizer writes (None: fp32 parity mode or the MLP mapper,
+        which keep their transpose launches)."""
+        f = self.flat
+        if f.flat_c is None or f.flat_c.dtype != torch.bfloat16 or not isinstance(self.mcore, TransformerMapperCore):
+            return None
+        base, end = f.flat_c.data_ptr(), f.flat_c.data_ptr() + 2 * f.n
+        items = []
+        for a, b in self.mcore.transpose_pairs():
+            if not (base <= a.data_ptr() < end and a.is_contiguous()):
+                return None
+            items.append(((a.data_ptr() - base) // 2, a.shape[0], a.shape[1], b))
+        return items
+
     def _optimizer(self) -> None:
         hp, f = self.hp, self.flat
+        items = self._adam_items() if ADAM_TRANSPOSE else None
         ops.adamw_step(f.flat, f.flat_grad, f.exp_avg, f.exp_avg_sq, self.adam_state, self.adam_ws, lr=hp.lr,
                        betas=hp.betas, eps=hp.eps, weight_decay=hp.weight_decay, max_norm=hp.max_norm,
                        num_warmup_steps=hp.num_warmup_steps, num_training_steps=hp.num_training_steps,
-                       bf16_out=f.flat_c)
-        self.mcore.refresh_transposes()
+                       bf16_out=f.flat_c, items=items)
+        if not items:
+            self.mcore.refresh_transposes()
         if self.gpt_trainable:
             self.gcore.refresh_from_flat()
 

@@ -321,9 +321,13 @@ class TransformerMapperCore:
         """Widest dW operand (transposed into DWHelper scratch): linear out Hl*D, qkv 3D, ff 4D."""
         return max(self.Hl * self.D, 4 * self.D, self.E)
 
+    def transpose_pairs(self):
+        """(weight [out, in], its transposed copy [in, out]) of every layer's four products."""
+        return [(a, b) for w in self.layers
+                for a, b in ((w.in_w, w.in_wt), (w.out_w, w.out_wt), (w.l1_w, w.l1_wt), (w.l2_w, w.l2_wt))]
+
     def refresh_transposes(self) -> None:
-        pairs = [(a, b) for w in self.layers
-                 for a, b in ((w.in_w, w.in_wt), (w.out_w, w.out_wt), (w.l1_w, w.l1_wt), (w.l2_w, w.l2_wt))]
+        pairs = self.transpose_pairs()
         if pairs and pairs[0][0].dtype == torch.bfloat16:
             ops.transpose_batch(pairs)  # one launch for every layer's copies (was 4 per layer)
         else:

@@ -689,8 +689,21 @@ def adamw_workspace(n: int) -> int:
 def adamw_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, state: Tensor,
                workspace: Tensor, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                weight_decay: float = 0.01, max_norm: float = 1.0, num_warmup_steps: int = 0,
-               num_training_steps: int = 1, bf16_out: Optional[Tensor] = None) -> None:
+               num_training_steps: int = 1, bf16_out: Optional[Tensor] = None, items=None) -> None:
+    """items: (flat offset, rows, cols, dst) of row-major matrices inside params whose transposed bf16 copy
+    dst = bf16_out[offset:offset + rows*cols].view(rows, cols)^T the update writes too (icap_adamw_args.items:
+    the update kernel itself where it can tile the matrix, icap_transpose_batch inside the call otherwise)."""
     a = AdamWArgs()
+    arr = None
+    if items:
+        if bf16_out is None:
+            raise L.IcapError("adamw_step: items need bf16_out")
+        arr = (L.AdamWItem * len(items))()
+        for it, (off, rows, cols, dst) in zip(arr, items):
+            if dst.dtype != torch.bfloat16 or dst.dim() != 2 or tuple(dst.shape) != (cols, rows):
+                raise L.IcapError("adamw_step: an item's dst must be a bf16 [cols, rows] matrix")
+            it.offset, it.rows, it.cols, it.dst, it.ldd = off, rows, cols, dst.data_ptr(), _ld(dst)
+        a.n_items, a.items = len(items), C.cast(arr, C.c_void_p)
     a.n = params.numel()
     a.params, a.grads, a.exp_avg, a.exp_avg_sq = (params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(),
                                                   exp_avg_sq.data_ptr())

@@ -358,7 +358,17 @@ int icap_cross_entropy(int32_t dtype, int64_t rows, int64_t V, const void* logit
 /* state layout (float/int64 view): [0]=int64 step (completed steps),         */
 /* [2]=f32 last grad norm, [3]=f32 clip coef, [4]=f32 lr used, [5]=f32 step   */
 /* size lr/bc1, [6]=f32 sqrt(bc2), [7]=f32 decay factor 1-lr*wd.              */
+/* items (optional, needs bf16_out): row-major [rows, cols] matrices at flat   */
+/* element `offset` whose transposed bf16 copy dst[c*ldd + r] the update       */
+/* writes beside bf16_out (bitwise icap_transpose_batch of that bf16_out).     */
+/* Items must not overlap. Up to 32 items with offset % 8, rows % 64, cols % 8 */
+/* and ldd % 8 == 0, ldd >= rows and 16-byte aligned bf16_out / dst are        */
+/* written by the update kernel itself; any other item is transposed by        */
+/* icap_transpose_batch after it. n_items == 0: the call as it always was.     */
 /* ------------------------------------------------------------------------- */
+typedef struct {
+  int64_t offset; int64_t rows; int64_t cols; void* dst; int64_t ldd;
+} icap_adamw_item;
 typedef struct {
   int64_t n;
   float* params; float* grads; float* exp_avg; float* exp_avg_sq;
@@ -367,6 +377,8 @@ typedef struct {
   float lr, beta1, beta2, eps, weight_decay;
   float max_norm;           /* <= 0 disables clipping */
   int64_t num_warmup_steps, num_training_steps;
+  int32_t n_items;               /* 0: no transposed copies */
+  const icap_adamw_item* items;  /* host array of n_items, or NULL */
 } icap_adamw_args;
 size_t icap_adamw_workspace_bytes(int64_t n);
 int icap_adamw_step(const icap_adamw_args* a, void* workspace, void* stream);
