@@ -54,6 +54,18 @@ struct Geo {
 };
 }  // namespace g8p
 
+// Diagnostic builds only (make stamps: -DICAP_STAMPS): the tile kernel's phase stamps (gemm_tile.h: 8 uint64 per
+// blockIdx.x; [1] start, [2] first K-tile landed, [3] = [4] main loop done, [6] first row's stores issued, [5] end)
+#ifdef ICAP_STAMPS
+#define G8P_STAMP(i)                                                                                              \
+  do {                                                                                                            \
+    if (p.diag_stamps && threadIdx.x == 0)                                                                        \
+      p.diag_stamps[(int64_t)blockIdx.x * 8 + (i)] = (uint64_t)__builtin_amdgcn_s_memrealtime();                  \
+  } while (0)
+#else
+#define G8P_STAMP(i) do {} while (0)
+#endif
+
 #define G8P_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
 
 template <typename TC, int BN, int ACT>
@@ -82,6 +94,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(icap_gemm_args p, int ti
   const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+  G8P_STAMP(1);
   const int64_t mr = Mv - m0 < BM ? Mv - m0 : BM, nr = N - n0 < BN ? N - n0 : BN;
   const int nk = (int)((K + 63) / 64);
   const bf16_t* Ag = reinterpret_cast<const bf16_t*>(p.A);
@@ -258,6 +271,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(icap_gemm_args p, int ti
   // wave-row 1 runs one barrier behind wave-row 0: on every SIMD one wave's MFMAs overlap the other's reads
   if (wr == 1) __builtin_amdgcn_s_barrier();
   G8P_FENCE();
+  G8P_STAMP(2);
 
   for (int t = 0; t < nk; ++t) {
     const uint32_t tb = sbase + (uint32_t)((t % NBUF) * TB);
@@ -311,6 +325,8 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(icap_gemm_args p, int ti
     G8P_FENCE();
   }
   if (wr == 0) __builtin_amdgcn_s_barrier();  // equal barrier counts: wave-row 0 waits for row 1's last phase
+  G8P_STAMP(3);
+  G8P_STAMP(4);
 #undef G8P_FENCE
 
   // ---- epilogue: no DMA outstanding (the last wait was vmcnt(0)); every wave is past the last barrier ----------
@@ -358,6 +374,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(icap_gemm_args p, int ti
         for (int e = 0; e < 8; ++e) x[e] = rs * (x[e] - mean * wsum8[e]);
       }
       if (ok) epiw<TC, 8, AK>(p, grow, gcol, x, bias8, fullw, seed, drop_thresh, inv_keep);
+      if (qm == 0 && it == 0) G8P_STAMP(6);
       if constexpr (LNX == 1) {
         // producer: (mean, M2) of the STORED (rounded) values over this row's 32-column group = 4 lanes x 8
         float xr[8], sm = 0.f;
@@ -383,6 +400,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(icap_gemm_args p, int ti
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   }
+  G8P_STAMP(5);
 }
 #undef G8P_RD
 

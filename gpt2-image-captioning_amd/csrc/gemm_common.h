@@ -112,6 +112,15 @@ __device__ __forceinline__ uint4 bload(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 
+// v summed over the lane's quad (lanes 4q .. 4q + 3), partner ^1 first, then ^2 — the order and the operands of
+// v += __shfl_xor(v, 1); v += __shfl_xor(v, 2), so the same bits — as two DPP quad_perm moves (layernorm.hip
+// half_sum) instead of the two ds_bpermute_b32 LDS round trips the shuffles lower to. Every lane of the wave active.
+__device__ __forceinline__ float quad_sum(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));  // ^1
+  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));  // ^2
+  return v;
+}
+
 // compile-time loop: f(std::integral_constant<int, I>) for I in [I0, N)
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {

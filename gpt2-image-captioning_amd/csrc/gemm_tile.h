@@ -35,7 +35,8 @@
 
 // Diagnostic builds only (make stamps: -DICAP_STAMPS): phase timestamps per workgroup into icap_gemm_args.diag_stamps
 // (8 uint64 per blockIdx.x; s_memrealtime, 100 MHz): [0] split | order << 8 | tile << 32, [1] start, [2] first stage
-// landed, [3] main loop done, [4] split-K publish / combine done, [5] epilogue done. Not compiled otherwise.
+// landed, [3] main loop done, [4] split-K publish / combine done, [5] epilogue done, [6] the first row's stores issued
+// (after [4]: the first staging pass and whatever the first row waited for). Not compiled otherwise.
 #ifdef ICAP_STAMPS
 #define ICAP_STAMP(i, v)                                                                                         \
   do {                                                                                                         \
@@ -119,6 +120,11 @@ constexpr int roles_prefetch_groups(int nh, int rows_per_pass, int nhalf) {
     if (nh % g == 0 && (nh / g) * rows_per_pass / nhalf <= 4) return g;
   return nh;
 }
+// round 8: whether the MFMA waves of a ROLES block (tm x tn accumulators each, two fragment sets) can hold the epilogue's
+// operands (8 bias + 8 ln_wsum columns, up to 4 prefetched rows of 4 registers) through the main loop: not beside the
+// 128 accumulator + 96 fragment registers of variant 26's 64 x 128 wave tile, whose 8-wave block has 256 per wave
+// (with the columns alone it already spilled 13 registers: DESIGN.md, round 8)
+constexpr bool roles_hoist_fits(int tm, int tn) { return 4 * tm * tn + 8 * (tm + tn) <= 192; }
 
 template <typename TI, typename TC, int NST, int MINB, int WM, int WN, int TM, int TN, bool KOUT = false, int ACT = ACT_ANY,
           bool ROLES = false>
@@ -382,6 +388,74 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
     }
   };
 
+  // ---- epilogue operands under the main loop (round 8, HOIST: the split-role kernels with a bf16 C whose MFMA waves
+  // have the registers, roles_hoist_fits). A ROLES block has its CU to itself, so the round trip of what the epilogue
+  // loads before its first store — this lane's bias / ln_wsum columns, the dropout seed's device counter, the first
+  // prefetch group of resid / dact_src rows — was exposed once per tile. Both roles issue those loads here, in front of
+  // the ring of the tile they belong to (a block walks several tiles), into h_*; the epilogue below takes them from
+  // there instead of loading. An MFMA wave issues no other vector-memory operation but ln_prologue's and waits for
+  // them at their first use in the epilogue, long after they landed; for a loader wave see the counted waits of the
+  // ring. A ROLES tile has one K range or writes its split's slab (no fused combine), so it knows here whether it runs
+  // the whole epilogue. Same addresses, same clamp to row Mv - 1, same "never stored" rule as the loads they replace
+  // (the geometry below repeats the epilogue's: see there). Not the 8-MFMA-wave blocks of variant 28 (three waves per
+  // SIMD, 168 registers each) nor the K-outer weight gradients, which have no such operand.
+  constexpr bool HOIST = ROLES && NW == 4 && !KOUT && std::is_same<TC, bf16_t>::value && roles_hoist_fits(TM, TN);
+  // (the dispatching form ACT_ANY keeps pre[] in scratch — epiw takes it by pointer — and a copy loaded up here went
+  // there too, each load then waited for in front of the ring: its prefetch stays after the loop)
+  constexpr bool HOIST_PRE = HOIST && AK != ACT_ANY;
+  constexpr int H_NHALF = 2, H_EW = 8;                     // (HOIST: 4 MFMA + 4 loader waves, NHALF = 2)
+  constexpr int H_LPR = 16 * TN / H_EW, H_RPI = 64 / H_LPR;
+  constexpr int H_NEP = (16 * TM / EPR) / roles_prefetch_groups(16 * TM / EPR, EPR / H_RPI, H_NHALF) * (EPR / H_RPI);
+  float h_bias[H_EW], h_wsum[H_EW];
+  // the dropout seed's device counter, raw: eff_seed's arithmetic on it stays in the epilogue, and the load goes through
+  // the opaque thread index (tid >> 16 is 0) so that it is a per-lane value — a uniform one is moved to scalar
+  // registers right behind the load, with a vmcnt(0) wait in front of the ring
+  uint64_t h_ctr = 0;
+  uint4 h_pre[HOIST_PRE ? H_NEP / H_NHALF : 1];
+  auto hoist_operands = [&]() __attribute__((always_inline)) {
+    const bool whole = splits == 1;
+    if (whole && drop_thresh != 0u && p.seed_ptr) h_ctr = p.seed_ptr[tid >> 16];
+    const int ew = wave & (NW - 1), ewm = ew / WN, ewn = ew - ewm * WN, half = wave / NW;
+    const int er = lane / H_LPR, ec = (lane - er * H_LPR) * H_EW;
+    const int64_t col = n0 + ewn * 16 * TN + ec;
+#pragma unroll
+    for (int e = 0; e < H_EW; ++e) h_bias[e] = 0.f;
+    if (whole && p.bias && p.dact == ICAP_ACT_NONE) {
+#pragma unroll
+      for (int e = 0; e < H_EW; ++e) h_bias[e] = (col + e < N) ? p.bias[col + e] : 0.f;
+    }
+    if constexpr (LNX == 2) {
+#pragma unroll
+      for (int e = 0; e < H_EW; ++e) h_wsum[e] = (col + e < N) ? p.ln_wsum[col + e] : 0.f;
+    }
+    if constexpr (HOIST_PRE) {
+      const bf16_t* esrc = nullptr;
+      int64_t eld = 0;
+      if (whole) {
+        if (AK >= ACT_BWD) {
+          esrc = reinterpret_cast<const bf16_t*>(p.dact_src);
+          eld = p.ld_dact;
+        } else if (p.resid) {
+          esrc = reinterpret_cast<const bf16_t*>(p.resid);
+          eld = p.ldr;
+        }
+      }
+      const bool want_pre = esrc != nullptr && (eld % H_EW) == 0 && (reinterpret_cast<uintptr_t>(esrc) & 15) == 0 &&
+                            (p.ldc % H_EW) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
+      if (want_pre && col + H_EW <= N) {
+        const int64_t rb = m0 + ewm * 16 * TM + er;
+#pragma unroll
+        for (int i = 0; i < H_NEP; ++i) {
+          if ((i % (EPR / H_RPI)) % H_NHALF != half) continue;  // (the other wave's rows)
+          const int64_t r0 = rb + (int64_t)i * H_RPI;
+          const int64_t row = r0 < Mv ? r0 : Mv - 1;
+          h_pre[i / H_NHALF] = *reinterpret_cast<const uint4*>(esrc + row * eld + col);
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // keep the loads here: hipcc would sink each to its use
+  };
+
   if constexpr (ROLES) {
     // Split roles over an NST-stage LDS-DMA ring, one barrier per 64-deep k-step (tools/microbench/gemm_lab.hip,
     // profiles/r06_gemm_lab.txt). Barrier B_k (k = 0 .. nk) is reached by
@@ -399,6 +473,7 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
     constexpr int PA = BM / (8 * NLW);        // of them A rows (pieces i < PA)
     static_assert((BM + BN) % (8 * NLW) == 0 && BM % (8 * NLW) == 0 && (NST - 2) * P < 64, "roles: stage split");
     const uint32_t sbase = (uint32_t)reinterpret_cast<uintptr_t>(smem);
+    if constexpr (HOIST) hoist_operands();  // both roles, before the loaders' first issue() and the MFMA waves' ln_prologue
     if (wave >= NW) {
       const int lw = wave - NW;
       uint32_t voff[P];
@@ -437,6 +512,9 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
       };
 #pragma unroll
       for (int s = 0; s < NST - 1; ++s) issue(s, s);
+      // (round 8: the epilogue operand loads issued in front of the ring are older than every DMA piece, and
+      // vector-memory loads retire in issue order: once at most (NST - 2) P operations are outstanding they are the
+      // newest (NST - 2) P DMA pieces, so the counts below mean what they meant without those loads)
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * P) : "memory");
       __builtin_amdgcn_s_barrier();  // B_0
       for (int kt = 0; kt < nk; ++kt) {
@@ -773,7 +851,13 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
   const bool whole = splits == 1 || fused;  // this block applies the full epilogue (else: its split's slab)
 
   uint64_t seed = 0;
-  if (whole && drop_thresh != 0u) seed = eff_seed(p.seed, p.seed_ptr);
+  if constexpr (HOIST) {
+    // (the empty asm keeps eff_seed's arithmetic, and with it the wait for the counter's load, on this side of the loop)
+    uint32_t clo = (uint32_t)h_ctr, chi = (uint32_t)(h_ctr >> 32);
+    asm volatile("" : "+v"(clo), "+v"(chi));
+    const uint64_t ctr = ((uint64_t)chi << 32) | clo;
+    if (whole && drop_thresh != 0u) seed = eff_seed(p.seed, p.seed_ptr ? &ctr : nullptr);
+  } else if (whole && drop_thresh != 0u) seed = eff_seed(p.seed, p.seed_ptr);
   // split-K partial slab of this split (separate reduce pass): raw fp32 [M, N] (N % 4 == 0 is guaranteed by the host)
   float* slab = !whole ? reinterpret_cast<float*>(p.workspace) + (int64_t)split * M * N : nullptr;
 
@@ -799,7 +883,10 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
   float biasw[EW];
 #pragma unroll
   for (int e = 0; e < EW; ++e) biasw[e] = 0.f;
-  if (whole && p.bias && p.dact == ICAP_ACT_NONE) {
+  if constexpr (HOIST) {
+#pragma unroll
+    for (int e = 0; e < EW; ++e) biasw[e] = h_bias[e];
+  } else if (whole && p.bias && p.dact == ICAP_ACT_NONE) {
 #pragma unroll
     for (int e = 0; e < EW; ++e) biasw[e] = (col + e < N) ? p.bias[col + e] : 0.f;
   }
@@ -847,13 +934,21 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
     }
     want_pre = esrc != nullptr && (eld % EW) == 0 && (reinterpret_cast<uintptr_t>(esrc) & 15) == 0 &&
                (p.ldc % EW) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
-    prefetch(std::integral_constant<int, 0>{});
+    if constexpr (HOIST_PRE) {  // group 0 was loaded in front of the main loop (same rows, same condition)
+      static_assert(!HOIST_PRE || (NHALF == H_NHALF && EW == H_EW && NEP == H_NEP), "hoisted prefetch: the epilogue's geometry");
+      if (want_pre && fullw && storer) {
+#pragma unroll
+        for (int i = 0; i < NEP / NHALF; ++i) pre[i] = h_pre[i];
+      }
+    } else {
+      prefetch(std::integral_constant<int, 0>{});
+    }
   }
   // the consumer's epilogue factor: wsum of W gamma per output column (its row table came from the prologue)
   float wsumw[EW];
   if constexpr (LNX == 2) {
 #pragma unroll
-    for (int e = 0; e < EW; ++e) wsumw[e] = (col + e < N) ? p.ln_wsum[col + e] : 0.f;
+    for (int e = 0; e < EW; ++e) wsumw[e] = HOIST ? h_wsum[e] : ((col + e < N) ? p.ln_wsum[col + e] : 0.f);
   }
   if (NST == 1) __syncthreads();  // the single stage buffer is still being read by other waves
   // rows [EPR h, EPR h + EPR) of this wave's accumulator tile -> LDS (h compile-time: it indexes acc[])
@@ -900,8 +995,14 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
         xr[e] = ok ? bf2f(f2bf(x[e])) : 0.f;
         sm += xr[e];
       }
-      sm += __shfl_xor(sm, 1, 64);
-      sm += __shfl_xor(sm, 2, 64);
+      // (ROLES, round 8: the quad sums by DPP — __shfl_xor is a ds_bpermute_b32, an LDS round trip in the middle of the
+      // LDS-staged epilogue of a block with nothing else on its CU; the tile kernels at 3-4 blocks per CU keep it)
+      if constexpr (ROLES) {
+        sm = quad_sum(sm);
+      } else {
+        sm += __shfl_xor(sm, 1, 64);
+        sm += __shfl_xor(sm, 2, 64);
+      }
       const float mg = sm * (1.f / 32.f);
       float q2 = 0.f;
 #pragma unroll
@@ -909,8 +1010,12 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
         const float d = xr[e] - mg;
         q2 += d * d;
       }
-      q2 += __shfl_xor(q2, 1, 64);
-      q2 += __shfl_xor(q2, 2, 64);
+      if constexpr (ROLES) {
+        q2 = quad_sum(q2);
+      } else {
+        q2 += __shfl_xor(q2, 1, 64);
+        q2 += __shfl_xor(q2, 2, 64);
+      }
       if (ok && (lane & 3) == 0)
         reinterpret_cast<float2*>(p.ln_stats_out)[row * (N >> 5) + (col >> 5)] = make_float2(mg, q2);
     }
@@ -928,6 +1033,9 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
         constexpr int t = decltype(tc)::value;
         if ((NHALF == 1 || t % NHALF == half) && storer)
           store_row(h, t, (want_pre && fullw) ? &pre[((h % HPG) * (EPR / RPI) + t) / NHALF] : nullptr);
+#ifdef ICAP_STAMPS
+        if constexpr (h == 0 && t == 0) ICAP_STAMP(6, ICAP_NOW());
+#endif
       });
       __syncthreads();
     });
@@ -938,7 +1046,14 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
       __syncthreads();
       if (storer) {
 #pragma unroll 2
+#ifdef ICAP_STAMPS
+        for (int t = half; t < EPR / RPI; t += NHALF) {
+          store_row(h, t, nullptr);
+          if (h == 0 && t == 0) ICAP_STAMP(6, ICAP_NOW());
+        }
+#else
         for (int t = half; t < EPR / RPI; t += NHALF) store_row(h, t, nullptr);
+#endif
       }
       __syncthreads();
     });
