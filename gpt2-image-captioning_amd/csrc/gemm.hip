@@ -423,7 +423,7 @@ static int device_cus() {
 
 namespace icap {
 int gemm256_launch(const icap_gemm_args& p, uint32_t thr, float inv_keep, hipStream_t s);
-int gemm8p_launch(const icap_gemm_args& p, int bn, int actk, uint32_t thr, float inv_keep, hipStream_t s);
+int gemm8p_launch(const GemmPlan& pl, const icap_gemm_args& p, hipStream_t s);
 }
 
 // ICAP_GEMM_DIAG = 1 / 2 / 3: drop the A / B / both operands' staging loads of the tile kernels (zero-record
@@ -558,7 +558,7 @@ extern "C" int icap_gemm(const icap_gemm_args* a, void* stream) {
     return check_launch("icap_gemm(skinny)");
   }
   if (pl.g256) return gemm256_launch(p, thr, inv_keep, s);
-  if (pl.g8p) return gemm8p_launch(p, pl.g8p, pl.actk, thr, inv_keep, s);
+  if (pl.g8p) return gemm8p_launch(pl, p, s);
   const int sp = pl.splits;
   const int skew = gemm_plan_skew(p, pl, plan_diag());
   const int nks = pl.nk_split | (skew << 20) | (gemm_diag() << 28) | (gemm_acquire() << 30);

@@ -28,7 +28,10 @@
 // same half was read two or more phases earlier (buffer (u mod NBUF): for h0 at p2 of K-tile t, u = t + LA + 1 ≡ t),
 // so the WAR argument is unchanged; the RAW wait at p3 of K-tile t retires K-tile t + 1 and leaves everything issued
 // after its last half in flight (counted per wave: an A half-tile is 2 DMA instructions, a B half-tile BN / 128).
+#include <utility>
+
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 namespace icap {
 namespace g8p {
@@ -404,28 +407,28 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(icap_gemm_args p, int ti
 }
 #undef G8P_RD
 
-// host side: the forms the plan may pick (gemm.hip gemm8p_ok); BN 128 or 256
-int gemm8p_launch(const icap_gemm_args& p, int bn, int actk, uint32_t thr, float inv_keep, hipStream_t s) {
-  const int tiles_m = (int)((p.M + 255) / 256), tiles_n = (int)((p.N + bn - 1) / bn);
-  const dim3 grid((unsigned)(tiles_m * tiles_n)), block(512);
-#define G8P_GO(TC, BNV, A) hipLaunchKernelGGL((gemm8p_kernel<TC, BNV, A>), grid, block, 0, s, p, tiles_n, thr, inv_keep)
-#define G8P_ACT(TC, BNV)                                                                                  \
-  switch (actk) {                                                                                        \
-    case ACT_OFF: G8P_GO(TC, BNV, ACT_OFF); break;                                                       \
-    case ACT_FWD + ICAP_ACT_GELU_NEW: G8P_GO(TC, BNV, ACT_FWD + ICAP_ACT_GELU_NEW); break;               \
-    case ACT_BWD + ICAP_ACT_GELU_NEW: G8P_GO(TC, BNV, ACT_BWD + ICAP_ACT_GELU_NEW); break;               \
-    case ACT_LNS: G8P_GO(TC, BNV, ACT_LNS); break;                                                       \
-    case ACT_LNF: G8P_GO(TC, BNV, ACT_LNF); break;                                                       \
-    case ACT_LNF + ACT_FWD + ICAP_ACT_GELU_NEW: G8P_GO(TC, BNV, ACT_LNF + ACT_FWD + ICAP_ACT_GELU_NEW); break; \
-    default: G8P_GO(TC, BNV, ACT_ANY); break;                                                            \
+// host side: the forms of gemm_plan.h's table (g8p_form_exists), nothing else
+template <typename TC, int BN, int KIND>
+static bool gemm8p_launch_form(const GemmPlan& pl, const icap_gemm_args& p, hipStream_t s) {
+  if constexpr (g8p_form_exists(BN, dtype_of<TC>, KIND)) {
+    if (pl.actk != KIND) return false;
+    const int tiles_m = (int)((p.M + 255) / 256), tiles_n = (int)((p.N + BN - 1) / BN);
+    hipLaunchKernelGGL((gemm8p_kernel<TC, BN, KIND>), dim3((unsigned)(tiles_m * tiles_n)), dim3(512), 0, s, p, tiles_n, pl.thr,
+                       pl.inv_keep);
+    return true;
   }
-  if (p.c_dtype == ICAP_BF16) {
-    if (bn == 128) { G8P_ACT(bf16_t, 128) } else { G8P_ACT(bf16_t, 256) }
-  } else {
-    if (bn == 128) { G8P_ACT(float, 128) } else { G8P_ACT(float, 256) }
-  }
-#undef G8P_ACT
-#undef G8P_GO
+  return false;
+}
+template <int BN, int... I>
+static bool gemm8p_launch_kinds(const GemmPlan& pl, const icap_gemm_args& p, hipStream_t s, std::integer_sequence<int, I...>) {
+  if (pl.g8p != BN) return false;
+  return p.c_dtype == ICAP_BF16 ? (gemm8p_launch_form<bf16_t, BN, epi_kind_at(I)>(pl, p, s) || ...)
+                                : (gemm8p_launch_form<float, BN, epi_kind_at(I)>(pl, p, s) || ...);
+}
+int gemm8p_launch(const GemmPlan& pl, const icap_gemm_args& p, hipStream_t s) {
+  constexpr auto kinds = std::make_integer_sequence<int, N_EPI_KINDS>();
+  if (!gemm8p_launch_kinds<G8P_WIDTHS[0]>(pl, p, s, kinds) && !gemm8p_launch_kinds<G8P_WIDTHS[1]>(pl, p, s, kinds))
+    return gemm_no_instantiation(pl);
   return check_launch("icap_gemm(8-phase)");
 }
 

@@ -20,6 +20,10 @@ typedef int i32x8_t __attribute__((ext_vector_type(8)));
 struct fp8_t {
   uint8_t v;
 };
+// the icap dtype (ICAP_F32 / ICAP_BF16 / ICAP_FP8_MX) of an element type
+template <typename T> inline constexpr int dtype_of = ICAP_F32;
+template <> inline constexpr int dtype_of<bf16_t> = ICAP_BF16;
+template <> inline constexpr int dtype_of<fp8_t> = ICAP_FP8_MX;
 
 // One block-scaled MFMA 16x16x128 (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 A and B). Lane map, measured
 // (tools/microbench/mx_probe.hip + tools/mx_probe_check.py, profiles/r03_mx_probe_check.txt): lane l = (g = l >> 4,

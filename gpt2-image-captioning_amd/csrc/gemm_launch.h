@@ -1,12 +1,15 @@
-// The per-form launchers of the tile kernel (gemm_tile_*.hip: one translation unit per input form, so their
-// instantiations compile in parallel) and the helpers they are written with.
+// The launchers of the tile kernel (gemm_tile_*.hip: one translation unit per group of forms, so their instantiations
+// compile in parallel) and the one generic launcher they are written with: it instantiates what gemm_plan.h's table
+// of forms names, nothing else.
 #pragma once
-#include "gemm_common.h"
+#include <utility>
+
 #include "gemm_plan.h"
+#include "gemm_tile.h"
 
 namespace icap {
 // Launch the tile-kernel instantiation pl selects (grid pl.grid_x, block pl.block_x); nks = nk_split | skew / diag
-// bits. ICAP_ERR_ARG (gemm_no_instantiation) for a (variant, epilogue kind) the unit does not instantiate.
+// bits. ICAP_ERR_ARG (gemm_no_instantiation) for a form that does not exist or is not the unit's.
 int launch_tile_bf16(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s);  // variants 0/4/5/12/13/16
 int launch_tile_act(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s);   // specialised epilogues
 int launch_tile_kout(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s);  // K-outer (14 / 15)
@@ -31,24 +34,36 @@ struct GemmGroup {
 };
 void launch_group_kout(const GemmGroup& g, int cus, hipStream_t s);
 
+// The epilogue kinds a unit holds: the 128-row variants spread theirs over three units (gemm.hip tile_launcher).
+enum KindSet : int { KINDS_PLAIN = 1, KINDS_ACT = 2, KINDS_LN = 4, KINDS_ALL = 7 };
+constexpr int kind_set(int actk) { return actk >= ACT_LNS ? KINDS_LN : actk >= ACT_FWD ? KINDS_ACT : KINDS_PLAIN; }
+
+// Variant V with epilogue kind KIND, if that form exists (tile_form_exists), is one of the unit's KINDS and pl asks for
+// it; the template numbers are V's row of TILE_VARIANTS.
+template <typename TI, typename TC, int V, int KINDS, int KIND>
+bool launch_tile_form(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
+  if constexpr ((kind_set(KIND) & KINDS) != 0 && tile_form_exists(V, dtype_of<TI>, dtype_of<TC>, KIND)) {
+    if (pl.actk != KIND) return false;
+    constexpr TileVariantInfo t = *tile_variant(V);
+    hipLaunchKernelGGL((gemm_kernel<TI, TC, t.nst, t.minb, t.wm, t.wn, t.tm, t.tn, t.kout, KIND, t.roles>),
+                       dim3(pl.grid_x, pl.grid_y), dim3(pl.block_x), 0, s, p, pl.tiles_n, pl.splits, nks, pl.thr, pl.inv_keep);
+    return true;
+  }
+  return false;
+}
+template <typename TI, typename TC, int V, int KINDS, int... I>
+bool launch_tile_kinds(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s, std::integer_sequence<int, I...>) {
+  return (launch_tile_form<TI, TC, V, KINDS, epi_kind_at(I)>(pl, p, nks, s) || ...);
+}
+// The generic launcher: the forms of variants V... with input type TI, either C dtype, and the kinds of set KINDS.
+template <typename TI, int KINDS, int... V>
+int launch_tile_forms(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
+  constexpr auto kinds = std::make_integer_sequence<int, N_EPI_KINDS>();
+  const bool c16 = p.c_dtype == ICAP_BF16;
+  const bool done = ((pl.variant == V && (c16 ? launch_tile_kinds<TI, bf16_t, V, KINDS>(pl, p, nks, s, kinds)
+                                              : launch_tile_kinds<TI, float, V, KINDS>(pl, p, nks, s, kinds))) || ...);
+  return done ? ICAP_OK : gemm_no_instantiation(pl);
+}
+
 }  // namespace icap
 
-// The launch helpers of the gemm_tile_*.hip units (each defines its launcher with these).
-#define ICAP_TILE_PRELUDE                                       \
-  const dim3 grid(pl.grid_x, pl.grid_y), block(pl.block_x);     \
-  const int sp = pl.splits, tn = pl.tiles_n;                    \
-  const uint32_t thr = pl.thr;                                  \
-  const float inv_keep = pl.inv_keep
-#define ICAP_GK(TI, TC, NST, MINB, TM_, TN_, KOUT)                                                              \
-  do {                                                                                                       \
-    if (pl.actk == ACT_ANY) hipLaunchKernelGGL((gemm_kernel<TI, TC, NST, MINB, 2, 2, TM_, TN_, KOUT, ACT_ANY>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep); \
-    else if (pl.actk == ACT_OFF) hipLaunchKernelGGL((gemm_kernel<TI, TC, NST, MINB, 2, 2, TM_, TN_, KOUT, ACT_OFF>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep); \
-    else return gemm_no_instantiation(pl);                                                                     \
-  } while (0)
-#define ICAP_GEMM_LAUNCH(TI, TC)                                    \
-  switch (pl.variant) {                                             \
-    case V_DB: ICAP_GK(TI, TC, 2, 2, 4, 4, false); break;           \
-    case V_S3: ICAP_GK(TI, TC, 1, 3, 4, 4, false); break;           \
-    case V_S4: ICAP_GK(TI, TC, 1, 4, 4, 4, false); break;           \
-    default: return gemm_no_instantiation(pl);                      \
-  }

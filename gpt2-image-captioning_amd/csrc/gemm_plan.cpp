@@ -1,6 +1,7 @@
 // The GEMM launch planner: which kernel instantiation, grid and split-K one icap_gemm call takes. Host-only (no
 // HIP header; the planner never dereferences an operand pointer). gemm_plan validates the arguments, then tries one
-// rule per kernel family in a fixed order; a family either fills the plan or passes.
+// rule per kernel family in a fixed order; a family either fills the plan or passes. Which epilogue kinds a kernel has
+// is not written here: every family reads its variant's row of gemm_plan.h's table of forms.
 #include "gemm_plan.h"
 
 #include <cstdio>
@@ -123,18 +124,8 @@ static int require_split_workspace(const icap_gemm_args& p, int64_t splits) {
   return ICAP_OK;
 }
 
-// Which epilogue instantiations a kernel family has beside ACT_OFF and the runtime dispatch ACT_ANY (each must agree
-// with the switch of the family's launcher, which rejects any other kind).
-struct EpiCaps {
-  unsigned fwd = 0, bwd = 0;  // bit a: ACT_FWD + a / ACT_BWD + a (for bf16 row-major operands)
-  bool ln_producer = false;   // ACT_LNS (activation-free)
-  bool ln_consumer = false;   // ACT_LNF, activation-free or with ...
-  unsigned ln_fwd = 0;        // ... bit a: ACT_FWD + a
-  bool ln_any = false;        // ... the runtime dispatch
-  bool f32_c_plain = true;    // an fp32 C has ACT_OFF / ACT_ANY only
-};
-constexpr unsigned A_(int act) { return 1u << act; }
-// The epilogue kind (ACT_* | ACT_LNS / ACT_LNF) of the launch in a family of capabilities c, -1 where it has no form.
+// The epilogue kind (ACT_* | ACT_LNS / ACT_LNF) of the launch on a kernel of capabilities c (a row of gemm_plan.h's
+// table of forms), -1 where it has no form. Every kind it returns exists (epi_kind_exists; plan_check.cpp checks).
 static int epilogue_kind(const icap_gemm_args& p, const EpiCaps& c) {
   const bool wide_c = p.c_dtype != ICAP_BF16 && c.f32_c_plain;
   int a = plain(p) ? ACT_OFF : ACT_ANY;
@@ -224,8 +215,7 @@ static int plan_g8p(const PlanCtx& c, GemmPlan& pl) {
   if (!ring_operands(p) || p.split_k > 1) return PASS;
   if (p.M < 256 || p.K < 64 || p.path == 1 || p.path == 3 || p.path >= 6) return PASS;  // (6 ... 12: other forced forms)
   if (p.M * p.lda >= (1ll << 30) || p.N * p.ldb >= (1ll << 30)) return PASS;  // 32-bit DMA byte offsets per tile
-  constexpr EpiCaps caps = {A_(ICAP_ACT_GELU_NEW), A_(ICAP_ACT_GELU_NEW), true, true, A_(ICAP_ACT_GELU_NEW), false, false};
-  const int actk = epilogue_kind(p, caps);
+  const int actk = epilogue_kind(p, G8P_EPI);
   if (actk < 0) return PASS;
   int bn = p.path == 4 ? 128 : p.path == 5 ? 256 : 0;
   if (bn == 0) {
@@ -384,11 +374,7 @@ static int plan_roles(const PlanCtx& c, GemmPlan& pl) {
   // (no LayerNorm hand-off: it needs the whole epilogue in the kernel)
   const bool rsplit = p.split_k > 1 && !c.lnx && rv != V_ROLES192;
   if (!rv || p.M < tile_variant(rv)->bm() || !(p.split_k <= 1 || rsplit) || !ring_operands(p)) return PASS;
-  constexpr unsigned gelus = A_(ICAP_ACT_GELU_NEW) | A_(ICAP_ACT_QUICK_GELU), relu = A_(ICAP_ACT_RELU);
-  constexpr EpiCaps wide = {gelus, A_(ICAP_ACT_GELU_NEW), true, true, gelus};
-  constexpr EpiCaps wide192 = {gelus | relu, A_(ICAP_ACT_GELU_NEW) | relu, true, true, gelus};
-  constexpr EpiCaps narrow = {0, 0, true, false};
-  const int actk = epilogue_kind(p, rv == V_ROLES ? wide : rv == V_ROLES192 ? wide192 : narrow);
+  const int actk = epilogue_kind(p, tile_variant(rv)->epi);
   if (actk < 0) return PASS;
   if (rsplit) ICAP_REQUIRE(p.K > 0, "icap_gemm: K must be positive");
   const SplitRanges r = split_ranges(c.nk, rsplit ? p.split_k : 1);
@@ -404,9 +390,7 @@ static int plan_roles(const PlanCtx& c, GemmPlan& pl) {
 static int plan_r256(const PlanCtx& c, const TileSplit& ts, GemmPlan& pl) {
   const icap_gemm_args& p = c.p;
   if (!(ts.splits == 1 && p.M >= 256 && p.path == 6 && ring_operands(p))) return PASS;
-  constexpr unsigned gelus = A_(ICAP_ACT_GELU_NEW) | A_(ICAP_ACT_QUICK_GELU);
-  constexpr EpiCaps caps = {gelus, A_(ICAP_ACT_GELU_NEW), true, true, gelus};
-  const int actk = epilogue_kind(p, caps);
+  const int actk = epilogue_kind(p, tile_variant(V_R256)->epi);
   if (actk < 0) return PASS;
   fill_tile_plan(c, pl, V_R256, split_ranges(c.nk, 1), false, actk, false);
   return ICAP_OK;
@@ -439,14 +423,13 @@ static int plan_w192(const PlanCtx& c, const TileSplit& ts, GemmPlan& pl) {
     // slower — 12833 / 12811 vs 12876 / 12895 images/s, profiles/r05_w192_ab.txt — so the split stays.)
   }
   if (!(w24 && p.M >= 192 && ring_operands(p))) return PASS;
-  constexpr EpiCaps caps = {0, 0, true, false};
-  const int actk = epilogue_kind(p, caps);
-  if (actk < 0) return PASS;
   // K > 16 stages over one round of tiles: the 4-stage ring at one block per CU (ICAP_W192R = 2 in the
   // diagnostic build: never). Measured (profiles/r05_w192_ab.txt): GPT-2 c_attn dX 3584 x 768 x
   // 2304 28.1 µs on the ring, 33.0 double-buffered (29.4 with the automatic in-launch split-K); past one round
   // the double-buffered loop at 2 blocks per CU wins by far (CLIP fc2, 408 tiles: 48.2 vs 64.8 µs)
   const int v = c.nk > 16 && c.diag.w192r != 2 && t192 <= cus ? V_W192_RING : V_W192;
+  const int actk = epilogue_kind(p, tile_variant(v)->epi);
+  if (actk < 0) return PASS;
   fill_tile_plan(c, pl, v, split_ranges(c.nk, 1), false, actk, false);
   return ICAP_OK;
 }
@@ -505,13 +488,8 @@ static int tile128_variant(const PlanCtx& c, const TileSplit& ts) {
 // (gemm_tile_ln.hip): producers on 0 / 4 / 5 / 12 / 13; consumers there without an activation, with gelu_new on 0 / 4 /
 // 5, quick_gelu on 4, and the dispatching form on 12 / 13.
 static EpiCaps tile128_caps(int v, bool spec_act) {
-  constexpr unsigned gn = A_(ICAP_ACT_GELU_NEW), qg = A_(ICAP_ACT_QUICK_GELU), relu = A_(ICAP_ACT_RELU);
-  EpiCaps caps;
-  if (v == V_DB || v == V_S4) caps = {gn, gn, true, true, gn};
-  else if (v == V_S3) caps = {gn | qg | A_(ICAP_ACT_GELU_ERF), gn, true, true, gn | qg};
-  else if (v == V_N13) caps = {relu, relu, true, true, 0, true};
-  else if (v == V_N12) caps = {0, 0, true, true, 0, true};
-  if (!spec_act) caps.fwd = caps.bwd = 0;
+  EpiCaps caps = tile_variant(v)->epi;
+  if (!spec_act) caps.fwd = caps.bwd = 0;  // (diagnostic build) ICAP_SPEC_ACT = 0
   return caps;
 }
 // The 128-row tile kernels (variants 0 ... 16): every launch no other family took.
@@ -582,8 +560,9 @@ const char* gemm_plan_kernel_name(const icap_gemm_args& a, const GemmPlan& pl) {
 }
 
 int gemm_no_instantiation(const GemmPlan& pl) {
-  set_error("icap_gemm: no instantiation of tile variant " + std::to_string(pl.variant) + " with epilogue kind " +
-            std::to_string(pl.actk));
+  set_error("icap_gemm: no instantiation of " + (pl.g8p ? "the 8-phase kernel of width " + std::to_string(pl.g8p)
+                                                         : "tile variant " + std::to_string(pl.variant)) +
+            " with epilogue kind " + std::to_string(pl.actk) + " for these dtypes");
   return ICAP_ERR_ARG;
 }
 

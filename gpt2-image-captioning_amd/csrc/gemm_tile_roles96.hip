@@ -1,4 +1,3 @@
-#include "gemm_tile.h"
 #include "gemm_launch.h"
 
 namespace icap {
@@ -7,23 +6,7 @@ namespace icap {
 // waves, 5 stages of 28 KiB (three in flight), one block per CU. For the N <= 1024 products: 3584 x 768 is 38 x 6 = 228
 // tiles, one round over 256 CUs with no split of K (GPT-2's N = 768 products at K = 768 / 2304 / 3072).
 int launch_tile_roles96(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
-  ICAP_TILE_PRELUDE;
-#define ICAP_GKW(TC, KIND) \
-  hipLaunchKernelGGL((gemm_kernel<bf16_t, TC, 5, 1, 2, 2, 3, 4, false, KIND, true>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep)
-  if (p.c_dtype != ICAP_BF16) {
-    if (pl.actk == ACT_OFF) ICAP_GKW(float, ACT_OFF);
-    else if (pl.actk == ACT_ANY) ICAP_GKW(float, ACT_ANY);
-    else return gemm_no_instantiation(pl);
-    return ICAP_OK;
-  }
-  switch (pl.actk) {
-    case ACT_OFF: ICAP_GKW(bf16_t, ACT_OFF); break;
-    case ACT_LNS + ACT_OFF: ICAP_GKW(bf16_t, ACT_LNS + ACT_OFF); break;
-    case ACT_ANY: ICAP_GKW(bf16_t, ACT_ANY); break;
-    default: return gemm_no_instantiation(pl);
-  }
-#undef ICAP_GKW
-  return ICAP_OK;
+  return launch_tile_forms<bf16_t, KINDS_ALL, V_ROLES96>(pl, p, nks, s);
 }
 
 }  // namespace icap

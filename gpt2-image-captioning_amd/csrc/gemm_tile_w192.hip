@@ -1,4 +1,3 @@
-#include "gemm_tile.h"
 #include "gemm_launch.h"
 
 namespace icap {
@@ -12,28 +11,7 @@ namespace icap {
 // block per CU) for long K. (Round 5 also measured a fragment prefetch across the ring's stages and a register-staged
 // double buffer on these tiles — bitwise equal, neither faster: profiles/r05_w192_ab.txt; removed.)
 int launch_tile_w192(const GemmPlan& pl, const icap_gemm_args& p, int nks, hipStream_t s) {
-  ICAP_TILE_PRELUDE;
-#define ICAP_GKW(TC, KIND)                                                                                                 \
-  do {                                                                                                                     \
-    if (pl.variant == V_W192_RING)                                                                                         \
-      hipLaunchKernelGGL((gemm_kernel<bf16_t, TC, 4, 1, 4, 1, 3, 4, false, KIND>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep); \
-    else                                                                                                                   \
-      hipLaunchKernelGGL((gemm_kernel<bf16_t, TC, 2, 2, 4, 1, 3, 4, false, KIND>), grid, block, 0, s, p, tn, sp, nks, thr, inv_keep); \
-  } while (0)
-  if (p.c_dtype != ICAP_BF16) {
-    if (pl.actk == ACT_OFF) ICAP_GKW(float, ACT_OFF);
-    else if (pl.actk == ACT_ANY) ICAP_GKW(float, ACT_ANY);
-    else return gemm_no_instantiation(pl);
-    return ICAP_OK;
-  }
-  switch (pl.actk) {
-    case ACT_OFF: ICAP_GKW(bf16_t, ACT_OFF); break;
-    case ACT_LNS + ACT_OFF: ICAP_GKW(bf16_t, ACT_LNS + ACT_OFF); break;
-    case ACT_ANY: ICAP_GKW(bf16_t, ACT_ANY); break;
-    default: return gemm_no_instantiation(pl);
-  }
-#undef ICAP_GKW
-  return ICAP_OK;
+  return launch_tile_forms<bf16_t, KINDS_ALL, V_W192, V_W192_RING>(pl, p, nks, s);
 }
 
 }  // namespace icap

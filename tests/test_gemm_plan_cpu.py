@@ -22,17 +22,32 @@ SNAPSHOT = os.path.join(ROOT, "tests", "golden", "gemm_plan_snapshot.json")
 # into gemm_plan.cpp, and is unchanged since. ALL includes those inputs.
 PINNED = ("80daf59005194f16", 25984512)
 ALL = ("d5039a960bf6e0a0", 29360640)
+# The third sweep (fp32 / MX / K-outer operands with activations, the LayerNorm hand-off, each under the PlanDiag
+# overrides of the diagnostic build): recorded on the planner as it was before its epilogue rules and the launchers
+# were derived from gemm_plan.h's table of forms, and unchanged by that.
+DIAG = ("6d7b54d04d099b7e", 1119744)
+# Every form of the table is planned by some case, but the six 8-phase forms with the LayerNorm hand-off and an fp32 C
+# (instantiated; gemm_validate takes the hand-off with a bf16 C only).
+COVERAGE = "forms 165 planned 159 unplannable 6"
+# The forms only a non-default PlanDiag plans (the diagnostic build): variant 5, 128 x 128 tiles at 4 blocks / CU.
+_V5 = "icap::gemm_kernel<%s, %s, 1, 4, 2, 2, 4, 4, false, %d>"
+DIAG_ONLY = sorted([_V5 % (ti, tc, k) for ti in ("float", "unsigned short") for tc in ("float", "unsigned short") for k in (0, 1)] +
+                   [_V5 % ("unsigned short", "unsigned short", k) for k in (17, 33, 256, 512, 529)])
 
 
 def test_plan_check_hashes(tmp_path):
     """The checker (host compiler, ASan + UBSan, its own main; nothing is loaded into Python) sweeps about 29 M
     argument combinations at 256 compute units, asserts splits >= 1, splits x nk_split covering K, a non-empty grid
-    and block, fused only with tickets — and prints one hash over every return code, error text and plan."""
+    and block, fused only with tickets, and that the table of forms has the instantiation each plan names — and
+    prints one hash over every return code, error text and plan of each sweep, then how many of the table's forms
+    were planned (it exits non-zero if one that can be was not) and which only under a PlanDiag override."""
     exe = str(tmp_path / "plan_check")
     subprocess.check_call(["make", "-s", "-C", CSRC, "plan_check", f"PLAN_CHECK={exe}"])
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    got = dict((k, (h, int(n))) for k, h, n in re.findall(r"^(pinned|all) ([0-9a-f]{16}) cases (\d+)$", out, re.M))
-    assert got == {"pinned": PINNED, "all": ALL}, out
+    got = dict((k, (h, int(n))) for k, h, n in re.findall(r"^(pinned|all|diag) ([0-9a-f]{16}) cases (\d+)$", out, re.M))
+    assert got == {"pinned": PINNED, "all": ALL, "diag": DIAG}, out
+    assert re.findall(r"^forms .*$", out, re.M) == [COVERAGE], out
+    assert sorted(re.findall(r"^diag-only (.*)$", out, re.M)) == DIAG_ONLY and len(DIAG_ONLY) == 13, out
 
 
 def test_snapshot_through_the_public_queries():
