@@ -172,8 +172,10 @@ def test_packed_step_equals_padded(dev, dtype, graph):
 
 
 def test_packed_step_with_dropout_runs(dev):
-    """Dropout on: the packed step draws its masks by packed row (a different, equally distributed draw from the
-    padded layout's), so only finiteness and descent are checked."""
+    """Dropout on: the packed step draws its [B, S, D] masks by packed row (a different, equally distributed draw
+    from the padded layout's), so it cannot be compared with the padded step; here 12 graph-replayed steps stay finite
+    and descend. The masks themselves are pinned elsewhere: test_dropout_step_gpu.py compares this step's loss and
+    gradients with the fp64 oracle drawing the same packed-row masks."""
     ids, mask, labels, emb = ragged_batch(7, 12, TINY_G.vocab_size, TINY_G.eos, TINY_M.embed_dim, seed=4)
     model = build(TINY_G, TINY_M, torch.float32, dev)
     t = CaptionTrainer(model, 7, 12, lr=3e-3, num_training_steps=20, dropout=True, seed=2)
