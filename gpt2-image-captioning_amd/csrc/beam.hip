@@ -73,9 +73,13 @@ __global__ __launch_bounds__(256) void beam_rowtop_kernel(int64_t V, const T* __
     if (x > v[K - 1]) {  // insertion into the sorted register list (compile-time indices)
       float cv = x;
       int32_t ci = (int32_t)j;
+      // from the insertion point on every entry moves down one place: a displaced entry that equals the next one
+      // must still go ahead of it (it has the lower index), so the shift cannot stop at a tie
+      bool ins = false;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        if (cv > v[k]) {
+        ins = ins || cv > v[k];
+        if (ins) {
           const float tv = v[k]; const int32_t ti = id[k];
           v[k] = cv; id[k] = ci; cv = tv; ci = ti;
         }
