@@ -9,7 +9,8 @@ owns device memory, streams, graphs and torch.distributed.
 __version__ = "0.1.0"
 
 from .clip import CLIPVisionConfig, CLIPVisionTower, extract_clip_embedding_from_image, extract_clip_embeddings, load_clip_model  # noqa: E402,F401
-from .clip_text import (CLIPTextConfig, CLIPTextTower, extract_caption_embeddings,  # noqa: E402,F401
+from .clip_text import (CLIPTextConfig, CLIPTextTower, ClipTextCore, chunk_captions,  # noqa: E402,F401
+                        extract_caption_embeddings,
                         extract_clip_embedding_from_caption, get_image_id_from_filename, load_captions_annotations,
                         load_clip_text_model, load_image_embeddings_file_names, map_caption_id_to_caption)
 from .dataset import CocoDataset, SyntheticCaptionDataset  # noqa: E402,F401

@@ -1,16 +1,19 @@
-"""CLIP text tower parameters and the caption-embedding file (src/embeddings/word_embeddings.py) — the host half.
+"""CLIP text tower (the text half of HF CLIPModel) on the icap HIP kernels, and the caption-embedding file
+(src/embeddings/word_embeddings.py).
 
-`CLIPTextTower` holds the text half of HF CLIPModel under HF's own key names (text_model.*, text_projection.weight),
-so an HF checkpoint loads directly, with a closed-form `random_init` whose outputs transformers' CLIPModel pins in
+`CLIPTextTower` holds the parameters under HF's own key names (text_model.*, text_projection.weight), so an HF
+checkpoint loads directly, with a closed-form `random_init` whose outputs transformers' CLIPModel pins in
 tests/golden/clip_text_*.npz (tools/make_clip_text_goldens.py). The extraction functions mirror the reference
 (`extract_clip_embedding_from_caption` and the helpers of word_embeddings.py:11-82, and its `__main__` block :85-171
 as `extract_caption_embeddings`) and write the structured caption file that `build_retrieval_store` reads.
 
-The device schedule of the tower (HF/models/clip/modeling_clip.py: CLIPTextEmbeddings :221-256 -> 12 causal pre-LN
-layers :353-384 -> final_layer_norm :559 -> the EOT row :561-582 -> text_projection :713) is not part of this
-build: `CLIPTextTower.get_text_features` raises (there is no host fallback). The extraction functions take any
-`clip_model` with `get_text_features` / `embed`, so they run today over another implementation of the tower and
-over this one once its schedule is in ("CLIP text tower").
+`ClipTextCore` is the device schedule (HF/models/clip/modeling_clip.py: CLIPTextEmbeddings :221-256 -> 12 causal
+pre-LN layers :353-384 -> final_layer_norm :559 -> the EOT row :561-582 -> text_projection :713). It runs on the
+padded [B, L] grid the caller passes: every launch extent, workspace size and row count is a host value, a call is
+processed in chunks of whole captions of at most ROWS_CAP token rows (`chunk_captions`), and the GEMM plans reachable
+under that cap are a closed set that tests/golden/clip_text_plan_cover.json lists and tests/test_clip_text_gpu.py
+runs one by one ("CLIP text tower"). The tower is causal and pools one row per caption, so the rows past
+the pooled position are computed and ignored. There is no host path.
 """
 
 from __future__ import annotations
@@ -18,16 +21,46 @@ from __future__ import annotations
 import json
 from collections import defaultdict
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import ops
 from .clip import _Encoder
 from .weights import det_tensor
 
 Tensor = torch.Tensor
+
+# The most token rows (B * L) and captions one chunk of the schedule holds: the reference's batch of 256 captions
+# (word_embeddings.py:112) at up to 32 tokens. A condition, not a tuned value: the GEMM planner picks its kernel by
+# M, and tests/golden/clip_text_plan_cover.json lists every plan it picks for M <= ROWS_CAP (the token-row GEMMs)
+# and M <= CAPTIONS_CAP (the pooled-row GEMMs), each of which tests/test_clip_text_gpu.py runs.
+ROWS_CAP = 8192
+CAPTIONS_CAP = 256
+
+
+def chunk_captions(B: int, L_: int, rows_cap: int = ROWS_CAP, captions_cap: int = CAPTIONS_CAP) -> List[Tuple[int, int]]:
+    """[(b0, b1)]: the captions of a [B, L] call in order, in chunks of whole captions with at most rows_cap token
+    rows and at most captions_cap captions each (L = 77: 106 captions a chunk; L <= 32: 256)."""
+    if L_ < 1 or L_ > rows_cap:
+        raise ValueError(f"chunk_captions: L = {L_} outside 1 ... {rows_cap}")
+    per = min(captions_cap, rows_cap // L_)
+    return [(b0, min(B, b0 + per)) for b0 in range(0, B, per)]
+
+
+def schedule_gemms(c: "CLIPTextConfig") -> List[Tuple[str, int, int, int, dict]]:
+    """(kind, N, K, largest M, epilogue) of every GEMM form ClipTextCore.run launches: the token-row products of
+    each layer and (last layer) their pooled-row forms, which differ in M alone, then the projection into fp32.
+    tools/clip_text_plan_cover.py plans each for every M up to its largest."""
+    D, I = c.hidden_size, c.intermediate_size
+    return [("qkv", 3 * D, D, ROWS_CAP, {"bias": True}),
+            ("out", D, D, ROWS_CAP, {"bias": True, "resid": True}),
+            ("fc1", I, D, ROWS_CAP, {"bias": True, "act": L.ACT_QUICK_GELU}),
+            ("fc2", D, I, ROWS_CAP, {"bias": True, "resid": True}),
+            ("proj", c.projection_dim, D, CAPTIONS_CAP, {"c_f32": True})]
 
 
 @dataclass
@@ -73,6 +106,8 @@ class CLIPTextTower(nn.Module):
         self.text_projection = nn.Linear(self.config.hidden_size, self.config.projection_dim, bias=False)
         for p in self.parameters():
             p.requires_grad = False  # frozen encoder
+        self._core = None
+        self._core_key = None
 
     @classmethod
     def random_init(cls, config: Optional[CLIPTextConfig] = None, seed: int = 0) -> "CLIPTextTower":
@@ -120,19 +155,179 @@ class CLIPTextTower(nn.Module):
                 int(input_ids.min()) < 0 or int(input_ids.max()) >= c.vocab_size):
             raise ValueError(f"CLIP text tower: token ids outside the vocabulary [0, {c.vocab_size})")
 
+    def core(self, dtype: torch.dtype = torch.bfloat16) -> "ClipTextCore":
+        """The device schedule of this tower in `dtype` (built once per dtype and device). A tower whose parameters
+        are not on a GPU has none: there is no host path."""
+        if self.device.type != "cuda":
+            raise L.IcapError("CLIPTextTower: a host path of the CLIP text tower is not part of this build; move "
+                              "the tower to the device (there is no host fallback)")
+        key = (dtype, self.device)
+        if getattr(self, "_core", None) is None or self._core_key != key:
+            self._core = ClipTextCore(self, dtype)
+            self._core_key = key
+        return self._core
+
+    @torch.no_grad()
     def get_text_features(self, input_ids: Tensor, attention_mask: Optional[Tensor] = None,
                           compute_dtype: torch.dtype = torch.bfloat16) -> Tensor:
-        """Projected (un-normalised) text features [B, projection_dim] fp32. attention_mask is accepted and ignored:
-        the tower is causal and pools the EOT row, which no padding position can reach. Not part of this build: the
-        device schedule is left out, and there is no host fallback."""
+        """Projected (un-normalised) text features [B, projection_dim] fp32 on the tower's device. attention_mask
+        is accepted and ignored: the tower is causal and pools the EOT row, which no padding position can reach.
+        Host ids are checked against the vocabulary before anything runs; ids that arrive as a device tensor are
+        guarded inside the embedding kernel (an id outside the vocabulary reads nothing and is counted), and the
+        4-byte count is read back after the run: non-zero raises ValueError."""
         self.check_ids(input_ids)
-        raise L.IcapError("CLIPTextTower.get_text_features: the device schedule of the CLIP text tower is not part "
-                          "of this build (DESIGN.md, \"CLIP text tower\"); there is no host fallback")
+        return self.core(compute_dtype).features(input_ids, normalize=False)
 
+    @torch.no_grad()
     def embed(self, input_ids: Tensor, attention_mask: Optional[Tensor] = None,
               compute_dtype: torch.dtype = torch.bfloat16) -> Tensor:
         """L2-normalised features (src/embeddings/word_embeddings.py:75-78); see get_text_features."""
-        return self.get_text_features(input_ids, attention_mask, compute_dtype)
+        self.check_ids(input_ids)
+        return self.core(compute_dtype).features(input_ids, normalize=True)
+
+
+class ClipTextCore:
+    """refresh / alloc / run, shaped like ClipCore. Workspaces are allocated once, for ROWS_CAP token rows and
+    CAPTIONS_CAP captions; `alloc(B, L)` hands out views of them, so a chunk of any shape under the caps runs (and
+    is captured into a HIP graph) without an allocation."""
+
+    def __init__(self, m: CLIPTextTower, dtype: torch.dtype):
+        self.m, self.dtype = m, dtype
+        self.dev = m.device
+        L.require_device(self.dev)
+        c = m.config
+        self.c = c
+        self.D, self.H = c.hidden_size, c.num_attention_heads
+        self.hd = self.D // self.H
+        self.refresh()
+        self._buf = None
+        self._ws = {}
+
+    def _cvt(self, t: Tensor) -> Tensor:
+        if self.dtype == torch.float32:
+            return t.contiguous()
+        out = torch.empty(t.shape, dtype=self.dtype, device=self.dev)
+        ops.convert(t.contiguous(), out)
+        return out
+
+    @torch.no_grad()
+    def refresh(self):
+        """Re-read the tower's parameters (after load_state_dict): fused QKV weights in the compute dtype, fp32
+        tables, biases and LayerNorm parameters."""
+        tm = self.m.text_model
+        self.tok = tm.embeddings.token_embedding.weight.data.contiguous()
+        self.pos = tm.embeddings.position_embedding.weight.data.contiguous()
+        self.final = (tm.final_layer_norm.weight.data, tm.final_layer_norm.bias.data)
+        self.w_proj = self._cvt(self.m.text_projection.weight.data)
+        self.layers = []
+        for lay in tm.encoder.layers:
+            a = lay.self_attn
+            w = SimpleNamespace()
+            w.qkv_w = self._cvt(torch.cat([a.q_proj.weight.data, a.k_proj.weight.data, a.v_proj.weight.data], 0))
+            w.qkv_b = torch.cat([a.q_proj.bias.data, a.k_proj.bias.data, a.v_proj.bias.data], 0).contiguous()
+            w.out_w, w.out_b = self._cvt(a.out_proj.weight.data), a.out_proj.bias.data
+            w.fc1_w, w.fc1_b = self._cvt(lay.mlp.fc1.weight.data), lay.mlp.fc1.bias.data
+            w.fc2_w, w.fc2_b = self._cvt(lay.mlp.fc2.weight.data), lay.mlp.fc2.bias.data
+            w.ln1 = (lay.layer_norm1.weight.data, lay.layer_norm1.bias.data)
+            w.ln2 = (lay.layer_norm2.weight.data, lay.layer_norm2.bias.data)
+            self.layers.append(w)
+
+    def _buffers(self) -> SimpleNamespace:
+        if self._buf is None:
+            c, D, dt, dev = self.c, self.D, self.dtype, self.dev
+            e = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
+            R, Bc = ROWS_CAP, CAPTIONS_CAP
+            b = SimpleNamespace()
+            b.ids = e(R, dtype=torch.int64)
+            b.x, b.h1, b.a, b.o = e(R, D), e(R, D), e(R, D), e(R, D)
+            b.qkv = e(R, 3 * D)
+            b.f = e(R, c.intermediate_size)
+            # the last layer's pooled rows (one per caption)
+            b.op, b.xp, b.hp, b.ap, b.xc, b.pooled = (e(Bc, D) for _ in range(6))
+            b.fp = e(Bc, c.intermediate_size)
+            b.feat32 = e(Bc, c.projection_dim, dtype=torch.float32)
+            b.emb = e(Bc, c.projection_dim, dtype=torch.float32)
+            b.pooled_row = e(Bc, dtype=torch.int32)
+            b.oov = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._buf = b
+        return self._buf
+
+    def alloc(self, B: int, L_: int) -> SimpleNamespace:
+        """The workspace of one chunk: B captions of L tokens, B <= CAPTIONS_CAP and B * L <= ROWS_CAP. ws.ids is
+        the static id buffer a captured graph reads; ws.feat32 / ws.emb are its outputs; ws.oov counts the ids the
+        embedding kernel found outside the vocabulary since it was last zeroed."""
+        if B < 1 or B > CAPTIONS_CAP or L_ < 1 or L_ > self.c.max_position_embeddings or B * L_ > ROWS_CAP:
+            raise L.IcapError(f"ClipTextCore.alloc: a chunk holds 1 ... {CAPTIONS_CAP} captions, L within the position "
+                              f"table and at most {ROWS_CAP} token rows (got B = {B}, L = {L_})")
+        ws = self._ws.get((B, L_))
+        if ws is not None:
+            return ws
+        b, M = self._buffers(), B * L_
+        ws = SimpleNamespace(B=B, L=L_, M=M, ids=b.ids[:M].view(B, L_), oov=b.oov, pooled_row=b.pooled_row[:B])
+        for nm in ("x", "h1", "a", "o", "qkv", "f"):
+            setattr(ws, nm, getattr(b, nm)[:M])
+        for nm in ("op", "xp", "hp", "ap", "xc", "pooled", "fp", "feat32", "emb"):
+            setattr(ws, nm, getattr(b, nm)[:B])
+        if len(self._ws) >= 64:
+            self._ws.clear()
+        self._ws[(B, L_)] = ws
+        return ws
+
+    def run(self, ws, ids: Tensor) -> Tensor:
+        """Kernel schedule of one chunk over device ids int64 [ws.B, ws.L] (ws.ids, or any contiguous device
+        tensor); returns ws.emb (fp32, L2-normalised; ws.feat32 holds the un-normalised features). Graph-capturable:
+        no host sync, no allocation. It neither zeroes nor reads ws.oov: under a captured graph ids outside the
+        vocabulary are made harmless by the kernel (zero token term) and counted, and it is the caller who looks at
+        the count."""
+        c, D, B, L_, M = self.c, self.D, ws.B, ws.L, ws.M
+        if ids.shape != (B, L_) or ids.dtype != torch.int64 or not ids.is_cuda or not ids.is_contiguous():
+            raise L.IcapError("ClipTextCore.run: ids must be a contiguous device int64 tensor [ws.B, ws.L]")
+        eps = c.layer_norm_eps
+        ops.clip_text_embed(ids, self.tok, self.pos, c.eos_token_id, ws.x, ws.pooled_row, ws.oov)
+        scale = self.hd ** -0.5
+        nl = len(self.layers)
+        for i, w in enumerate(self.layers):
+            ops.layernorm_fwd(ws.x, w.ln1[0], w.ln1[1], eps, ws.a, None, None)
+            ops.gemm(ws.a, w.qkv_w, ws.qkv, bias=w.qkv_b)
+            ops.attention_fwd(ws.qkv, ws.o, B=B, S=L_, H=self.H, hd=self.hd, scale=scale, causal=True)
+            if i == nl - 1:
+                # last layer: only the pooled row of each caption reaches the output (modeling_clip.py:559-582), and
+                # every other row's keys / values were used above, so out_proj, LayerNorm 2 and the MLP run on those B
+                # rows alone — gathered, because which row it is depends on the ids
+                ops.rows_gather(ws.pooled_row, ws.o, ws.op, ws.x, ws.xp, n_src=M)
+                ops.gemm(ws.op, w.out_w, ws.hp, bias=w.out_b, resid=ws.xp)
+                ops.layernorm_fwd(ws.hp, w.ln2[0], w.ln2[1], eps, ws.ap, None, None)
+                ops.gemm(ws.ap, w.fc1_w, ws.fp, bias=w.fc1_b, act=L.ACT_QUICK_GELU)
+                ops.gemm(ws.fp, w.fc2_w, ws.xc, bias=w.fc2_b, resid=ws.hp)
+                break
+            ops.gemm(ws.o, w.out_w, ws.h1, bias=w.out_b, resid=ws.x)
+            ops.layernorm_fwd(ws.h1, w.ln2[0], w.ln2[1], eps, ws.a, None, None)
+            ops.gemm(ws.a, w.fc1_w, ws.f, bias=w.fc1_b, act=L.ACT_QUICK_GELU)
+            ops.gemm(ws.f, w.fc2_w, ws.x, bias=w.fc2_b, resid=ws.h1)
+        ops.layernorm_fwd(ws.xc, self.final[0], self.final[1], eps, ws.pooled, None, None)
+        ops.gemm(ws.pooled, self.w_proj, ws.feat32)
+        ops.l2norm_rows(ws.feat32, ws.emb)
+        return ws.emb
+
+    @torch.no_grad()
+    def features(self, input_ids: Tensor, normalize: bool = True) -> Tensor:
+        """[B, projection_dim] fp32 of a [B, L] call, chunk by chunk (chunk_captions). Ids that arrived as a device
+        tensor could not be checked on the host: the kernel's count of ids outside the vocabulary is read back once,
+        after the last chunk, and a non-zero count raises ValueError."""
+        on_device = input_ids.is_cuda
+        ids = input_ids.to(device=self.dev, dtype=torch.int64).contiguous()
+        B, L_ = ids.shape
+        out = torch.empty((B, self.c.projection_dim), dtype=torch.float32, device=self.dev)
+        self._buffers().oov.zero_()
+        for b0, b1 in chunk_captions(B, L_):
+            ws = self.alloc(b1 - b0, L_)
+            self.run(ws, ids[b0:b1])
+            out[b0:b1].copy_(ws.emb if normalize else ws.feat32)
+        if on_device and B:
+            bad = int(self._buffers().oov.item())
+            if bad:
+                raise ValueError(f"CLIP text tower: {bad} token ids outside the vocabulary [0, {self.c.vocab_size})")
+        return out
 
 
 # ------------------------------------------------------------ reference-shaped API (word_embeddings.py:11-171)

@@ -880,6 +880,47 @@ def l2norm_rows(x: Tensor, out: Tensor, rows: Optional[int] = None) -> Tensor:
     return out
 
 
+def clip_text_embed(ids: Tensor, tok: Tensor, pos: Tensor, eos_token_id: int, x: Tensor, pooled_row: Tensor,
+                    oov_count: Tensor) -> Tensor:
+    """x[b*L + t] = tok[ids[b, t]] + pos[t] and pooled_row[b] = b*L + the pooled position of caption b
+    (include/icap.h icap_clip_text_embed). ids int64 [B, L]; tok / pos fp32 tables; pooled_row int32 [B];
+    oov_count int32 [1], incremented once per id outside the vocabulary (that id's token term is zero)."""
+    B, L_ = ids.shape
+    D = tok.shape[1]
+    if ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise L.IcapError("clip_text_embed: ids must be contiguous int64 [B, L]")
+    for t in (tok, pos):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != D:
+            raise L.IcapError("clip_text_embed: tok / pos must be contiguous fp32 [rows, D]")
+    if pooled_row.dtype != torch.int32 or pooled_row.numel() < B or oov_count.dtype != torch.int32:
+        raise L.IcapError("clip_text_embed: pooled_row must be int32 [B] and oov_count int32 [1]")
+    if not x.is_contiguous() or x.numel() < B * L_ * D:
+        raise L.IcapError("clip_text_embed: x must be contiguous with at least B*L rows of D")
+    call("icap_clip_text_embed", dtype_code(x.dtype), B, L_, D, tok.shape[0], pos.shape[0], ids.data_ptr(),
+         tok.data_ptr(), pos.data_ptr(), eos_token_id, x.data_ptr(), pooled_row.data_ptr(), oov_count.data_ptr(),
+         _stream())
+    return x
+
+
+def rows_gather(rows: Tensor, src0: Tensor, dst0: Tensor, src1: Optional[Tensor] = None,
+                dst1: Optional[Tensor] = None, n_src: Optional[int] = None) -> None:
+    """dst[r] = src[rows[r]] for one or two (src, dst) pairs in one launch (include/icap.h icap_rows_gather).
+    rows int32 [R] on the device; n_src: the sources' row count (default src0.shape[0]) — an index outside it
+    stores a zero row."""
+    R, D = rows.shape[0], src0.shape[1]
+    n_src = src0.shape[0] if n_src is None else n_src
+    if rows.dtype != torch.int32 or (src1 is None) != (dst1 is None):
+        raise L.IcapError("rows_gather: rows must be int32; src1 and dst1 go together")
+    for s, d in ((src0, dst0),) + (((src1, dst1),) if src1 is not None else ()):
+        if s.dtype != src0.dtype or d.dtype != src0.dtype or s.shape[1] != D or d.shape[1] != D:
+            raise L.IcapError("rows_gather: sources and destinations must share a dtype and a row length")
+        if s.shape[0] < n_src or d.shape[0] < R:
+            raise L.IcapError("rows_gather: a source has fewer than n_src rows or a destination fewer than R")
+    call("icap_rows_gather", dtype_code(src0.dtype), R, D, n_src, rows.data_ptr(), src0.data_ptr(), _ld(src0),
+         dst0.data_ptr(), _ld(dst0), _p(src1), 0 if src1 is None else _ld(src1), _p(dst1),
+         0 if dst1 is None else _ld(dst1), _stream())
+
+
 def greedy_next(logits: Tensor, V: int, eos: int, finished: Tensor, tokens: Tensor, step: int,
                 wte: Optional[Tensor], wpe: Optional[Tensor], pos: int, D: int, x: Optional[Tensor],
                 forced: Optional[Tensor] = None) -> None:

@@ -464,6 +464,27 @@ int icap_l2norm_rows(int32_t dtype, int64_t rows, int64_t D, const void* x, int6
                      float* out, int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* CLIP text tower helpers (HF/models/clip/modeling_clip.py:221-256,561-582;  */
+/* reached through src/embeddings/word_embeddings.py:71-72,139).              */
+/* ------------------------------------------------------------------------- */
+/* CLIPTextEmbeddings (:221-256) and the pooled position of CLIPTextTransformer.forward (:561-582) on the padded
+ * [B, L] grid: x[b*L + t] = tok[ids[b,t]] + pos[t] (fp32 tables [vocab, D] / [npos, D], L <= npos; the sum in fp32,
+ * rounded once to dtype) and pooled_row[b] = b*L + p_b, with p_b the first maximum of the ids of caption b (as
+ * int32, HF's .to(torch.int)) when eos_token_id == 2, else the first position holding eos_token_id, 0 when there
+ * is none. An id outside [0, vocab) reads no table row: its token term is zero and *oov_count (device int32, the
+ * caller zeroes it) is incremented once for it. D % 4 == 0, B*L < 2^31. */
+int icap_clip_text_embed(int32_t dtype, int32_t B, int32_t L, int32_t D, int64_t vocab, int32_t npos,
+                         const int64_t* ids, const float* tok, const float* pos, int64_t eos_token_id, void* x,
+                         int32_t* pooled_row, int32_t* oov_count, void* stream);
+/* dst0[r] = src0[rows[r]] and (src1 != NULL) dst1[r] = src1[rows[r]] for r < R in one launch: rows of D elements
+ * (D % 4 == 0), row strides lds / ldd in elements (% 4 == 0), rows = device int32 [R]; an index outside [0, n_src)
+ * reads nothing and stores a zero row. The data-dependent row selection `last_hidden_state[arange(B), p_b]` of
+ * modeling_clip.py:566-582, applied one layer early to the attention output and the residual stream. */
+int icap_rows_gather(int32_t dtype, int32_t R, int32_t D, int64_t n_src, const int32_t* rows, const void* src0,
+                     int64_t lds0, void* dst0, int64_t ldd0, const void* src1, int64_t lds1, void* dst1,
+                     int64_t ldd1, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Greedy-decode step helpers (src/models.py:389-469).                        */
 /* ------------------------------------------------------------------------- */
 /* next[b] = finished[b] ? eos : (forced ? forced[b] : argmax_v(logits[b, :V]))  */
