@@ -13,6 +13,7 @@ from .clip_text import (CLIPTextConfig, CLIPTextTower, ClipTextCore, chunk_capti
                         extract_caption_embeddings,
                         extract_clip_embedding_from_caption, get_image_id_from_filename, load_captions_annotations,
                         load_clip_text_model, load_image_embeddings_file_names, map_caption_id_to_caption)
+from .jpeg import DeviceJpegDecoder, decode_jpeg, parse_jpeg  # noqa: E402,F401
 from .dataset import CocoDataset, SyntheticCaptionDataset  # noqa: E402,F401
 from .engine import CaptionTrainer  # noqa: E402,F401
 from .gpt2 import GPT2Config, GPT2LMHeadModel  # noqa: E402,F401

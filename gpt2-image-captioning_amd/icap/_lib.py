@@ -118,6 +118,35 @@ class BeamArgs(C.Structure):
     ]
 
 
+JPEG_OK, JPEG_UNSUPPORTED = 0, 3
+JPEG_LOOK_BITS = 9
+JPEG_STAGE_ENTROPY, JPEG_STAGE_IDCT, JPEG_STAGE_COLOUR, JPEG_STAGE_ALL = 1, 2, 4, 7
+
+
+class JpegHuff(C.Structure):
+    _fields_ = [("maxcode", i32 * 18), ("valoff", i32 * 18), ("look", C.c_uint16 * (1 << JPEG_LOOK_BITS)),
+                ("vals", C.c_uint8 * 256)]
+
+
+class JpegDesc(C.Structure):
+    _fields_ = [
+        ("height", i32), ("width", i32),
+        ("ncomp", i32),
+        ("hs", i32), ("vs", i32),
+        ("restart_interval", i32),
+        ("mcus_x", i32), ("mcus_y", i32),
+        ("nseg", i32),
+        ("blocks", i32),
+        ("dc_tab", i32 * 3), ("ac_tab", i32 * 3),
+        ("quant", (C.c_uint16 * 64) * 3),
+        ("huff", JpegHuff * 4),
+    ]
+
+
+class JpegSegment(C.Structure):
+    _fields_ = [("offset", i64), ("length", i64), ("first_mcu", i32), ("mcu_count", i32)]
+
+
 # name -> (restype, argtypes); must mirror include/icap.h exactly
 SIGNATURES = {
     "icap_last_error": (C.c_char_p, []),
@@ -180,7 +209,13 @@ SIGNATURES = {
     "icap_topk_rows": (C.c_int, [i64, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
     "icap_retrieval_aggregate": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, i64,
                                            vp, vp, vp, i64, vp]),
+    "icap_jpeg_parse": (C.c_int, [vp, i64, vp, vp, i64]),
+    "icap_jpeg_decode_host": (C.c_int, [vp, i64, vp, vp, vp, vp]),
+    "icap_jpeg_decode": (C.c_int, [i32, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
 }
+# the host-only JPEG unit, also built on its own (no HIP runtime behind it) for loader workers
+JPEG_HOST_LIB_PATH = os.environ.get("ICAP_JPEG_HOST_LIB") or os.path.join(_HERE, "libicap_jpeg_host.so")
+JPEG_HOST_FUNCTIONS = ("icap_jpeg_parse", "icap_jpeg_decode_host")
 
 _lib = None
 
@@ -208,6 +243,26 @@ def load(path: str = LIB_PATH, strict: bool = True) -> C.CDLL:
         fn.restype = res
         fn.argtypes = args
     _lib = lib
+    return lib
+
+
+_jpeg_host = None
+
+
+def load_jpeg_host(path: str = JPEG_HOST_LIB_PATH) -> C.CDLL:
+    """Load (once) libicap_jpeg_host.so: csrc/jpeg_host.cpp alone, linked against no HIP library, so a process that
+    only parses (a DataLoader worker) opens no device."""
+    global _jpeg_host
+    if _jpeg_host is not None:
+        return _jpeg_host
+    if not os.path.exists(path):
+        raise IcapError(f"libicap_jpeg_host.so not found at {path}: build it with "
+                        "`python -c 'import __graft_entry__ as g; g.build()'`")
+    lib = C.CDLL(path)
+    for name in JPEG_HOST_FUNCTIONS:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    _jpeg_host = lib
     return lib
 
 

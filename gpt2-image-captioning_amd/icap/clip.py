@@ -417,11 +417,11 @@ def extract_clip_embedding_from_image(image, clip_model: CLIPVisionTower, clip_p
 @torch.no_grad()
 def extract_clip_embeddings(image_dir: str, output_path: str, clip_model: CLIPVisionTower,
                             clip_processor: CLIPProcessor, batch_size: int = 32, num_workers: int = 4,
-                            device: Optional[torch.device] = None) -> None:
+                            device: Optional[torch.device] = None, device_decode: bool = False) -> None:
     """clip.py:79-149: every image of a directory -> {"filenames", "embeddings"} .pt file (same format, same file
     order). JPEG decode runs in `num_workers` DataLoader processes as in the reference (icap.images)."""
     from .images import extract_directory
 
     n = extract_directory(image_dir, output_path, clip_model.embed, clip_processor, clip_model.config.projection_dim,
-                          batch_size, num_workers, device or clip_model.device)
+                          batch_size, num_workers, device or clip_model.device, device_decode=device_decode)
     print(f"Saved {n} CLIP embeddings to {output_path}.")

@@ -469,11 +469,12 @@ def load_dinov3_models(model_weights_dir: Optional[str] = None, repo_or_dir: str
 @torch.no_grad()
 def extract_dino_embeddings(image_dir: str, output_path: str, dino_model: DINOv3ImageTower,
                             dino_processor: DinoImageProcessor, batch_size: int = 32, num_workers: int = 4,
-                            device: Optional[torch.device] = None) -> None:
+                            device: Optional[torch.device] = None, device_decode: bool = False) -> None:
     """dino.py:140-185: every image of a directory -> {"filenames", "embeddings"} .pt (L2-normalised features, the
     reference's format and file order; decode in `num_workers` DataLoader processes)."""
     from .images import extract_directory
 
     n = extract_directory(image_dir, output_path, dino_model.embed, dino_processor, dino_model.config.embedding_dim,
-                          batch_size, num_workers, device or dino_model.device, feature=FEATURE_NAME)
+                          batch_size, num_workers, device or dino_model.device, feature=FEATURE_NAME,
+                          device_decode=device_decode)
     print(f"Saving {n} embeddings to {output_path}...")

@@ -1040,3 +1040,28 @@ def clip_preprocess_packed(packed: Tensor, sizes, device, size: int = 224, crop:
     call("icap_clip_preprocess", n, px.data_ptr(), geo_t.data_ptr(), crop, max_rows, tmp.data_ptr(), m.data_ptr(),
          s.data_ptr(), out.data_ptr(), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------- JPEG decode
+def jpeg_decode(toc, blob: Tensor, coef: Tensor, planes: Tensor, out: Tensor, status: Tensor,
+                stages: int = L.JPEG_STAGE_ALL) -> None:
+    """icap_jpeg_decode over one packed batch on the device: `blob` (uint8, 16-byte aligned) holds the layout table,
+    descriptors, segments and file bytes at the offsets `toc` names (icap.jpeg.pack_batch); coef int16 / planes uint8
+    scratch of total blocks x 64; out: the packed RGB buffer; status int32 [n]. Allocates nothing. stages: a mask of
+    L.JPEG_STAGE_* (a single stage, for timing, runs on what the earlier ones left in coef / planes)."""
+    from . import jpeg as J
+
+    n = int(toc[J.TOC_N])
+    if n == 0:
+        return
+    if blob.dtype != torch.uint8 or blob.data_ptr() % 16 or not blob.is_contiguous():
+        raise L.IcapError("jpeg_decode: blob must be a contiguous, 16-byte aligned uint8 tensor")
+    if (coef.dtype, planes.dtype, out.dtype, status.dtype) != (torch.int16, torch.uint8, torch.uint8, torch.int32):
+        raise L.IcapError("jpeg_decode: coef int16, planes / out uint8, status int32")
+    if status.numel() < n or blob.numel() < toc[J.TOC_DATA] + toc[J.TOC_DATA_BYTES]:
+        raise L.IcapError("jpeg_decode: status or blob smaller than the batch")
+    base = blob.data_ptr()
+    call("icap_jpeg_decode", n, base + toc[J.TOC_DATA], toc[J.TOC_DATA_BYTES], base + toc[J.TOC_DESCS],
+         base + toc[J.TOC_SEGS], toc[J.TOC_TOTAL_SEGS], base + toc[J.TOC_LAYOUT], toc[J.TOC_MAX_SEGS],
+         toc[J.TOC_MAX_BLOCKS], toc[J.TOC_MAX_H], toc[J.TOC_MAX_W], coef.data_ptr(), planes.data_ptr(), out.data_ptr(),
+         status.data_ptr(), stages, _stream())

@@ -371,11 +371,11 @@ def extract_vit_embedding_from_image(image, vit_model: ViTImageTower, vit_proces
 @torch.no_grad()
 def extract_vit_embeddings(image_dir: str, output_path: str, vit_model: ViTImageTower,
                            vit_processor: ViTImageProcessor, batch_size: int = 32, num_workers: int = 4,
-                           device: Optional[torch.device] = None) -> None:
+                           device: Optional[torch.device] = None, device_decode: bool = False) -> None:
     """vit.py:80-137: every image of a directory -> {"filenames", "embeddings"} .pt file (the reference's format and
     file order; decode in `num_workers` DataLoader processes)."""
     from .images import extract_directory
 
     n = extract_directory(image_dir, output_path, vit_model.embed, vit_processor, vit_model.config.embedding_dim,
-                          batch_size, num_workers, device or vit_model.device)
+                          batch_size, num_workers, device or vit_model.device, device_decode=device_decode)
     print(f"Saved {n} ViT embeddings to {output_path}.")

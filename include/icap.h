@@ -605,6 +605,81 @@ int icap_retrieval_aggregate(int32_t B, int32_t D, int32_t K, int32_t top_i, int
                              const float* query, int64_t ldq, float* retrieved, int32_t* cap_ids, float* out,
                              int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Baseline JPEG decode on the device (the reference    */
+/* decodes with PIL in its DataLoader workers, src/utils.py:119-173). The     */
+/* output equals Pillow's Image.open(f).convert("RGB") byte for byte:         */
+/* libjpeg's islow IDCT, fancy upsampling and fixed-point colour transform    */
+/* (csrc/jpeg_common.h).                                                      */
+/* ------------------------------------------------------------------------- */
+enum { ICAP_JPEG_OK = 0, ICAP_JPEG_UNSUPPORTED = 3 };
+/* icap_jpeg_decode's stages: ICAP_JPEG_STAGE_ALL decodes; a single stage runs that launch alone on the buffers  */
+/* the earlier stages filled (tools/jpeg_extract_bench.py times each between events)                              */
+enum { ICAP_JPEG_STAGE_ENTROPY = 1, ICAP_JPEG_STAGE_IDCT = 2, ICAP_JPEG_STAGE_COLOUR = 4, ICAP_JPEG_STAGE_ALL = 7 };
+#define ICAP_JPEG_LOOK_BITS 9
+#define ICAP_JPEG_MAX_DIM 16384
+/* One Huffman table in canonical form. A code of length l <= 9 is found through look[next 9 bits] =            */
+/* length << 8 | symbol (0: the code is longer); a longer one is the first l with (next l bits) <= maxcode[l],   */
+/* and its symbol is vals[valoff[l] + (next l bits)]. maxcode[l] is -1 where no code has length l.               */
+typedef struct icap_jpeg_huff {
+  int32_t maxcode[18];
+  int32_t valoff[18];
+  uint16_t look[1 << ICAP_JPEG_LOOK_BITS];
+  uint8_t vals[256];
+} icap_jpeg_huff;
+/* What icap_jpeg_parse found: one interleaved baseline scan of ncomp = 1 (grayscale) or 3 (YCbCr) components,   */
+/* luma sampled hs x vs (1x1, 2x1 or 2x2; grayscale: 1x1), chroma 1x1. The scan is mcus_x x mcus_y MCUs in       */
+/* nseg entropy segments (one per restart interval). blocks = the 8 x 8 blocks of all components at their        */
+/* padded sizes (whole MCUs): the image needs blocks * 64 int16 coefficients and blocks * 64 bytes of planes.    */
+/* quant[c]: component c's quantisation table in natural order; huff: DC 0, DC 1, AC 0, AC 1.                    */
+typedef struct icap_jpeg_desc {
+  int32_t height, width;
+  int32_t ncomp;
+  int32_t hs, vs;
+  int32_t restart_interval;
+  int32_t mcus_x, mcus_y;
+  int32_t nseg;
+  int32_t blocks;
+  int32_t dc_tab[3], ac_tab[3];
+  uint16_t quant[3][64];
+  icap_jpeg_huff huff[4];
+} icap_jpeg_desc;
+/* One entropy segment: bytes [offset, offset + length) of the file, MCUs [first_mcu, first_mcu + mcu_count).    */
+typedef struct icap_jpeg_segment {
+  int64_t offset, length;
+  int32_t first_mcu, mcu_count;
+} icap_jpeg_segment;
+/* Host only (no device is opened; also built as libicap_jpeg_host.so for loader workers). Walks the markers of   */
+/* data[0, size) and fills *desc and, when segs is not NULL, segs[0, desc->nseg) (call once with segs = NULL to   */
+/* learn nseg). Returns ICAP_JPEG_OK, or ICAP_JPEG_UNSUPPORTED for everything the device path does not decode     */
+/* (the caller decodes those with PIL): not SOF0 8-bit, arithmetic coding, 4 components, an Adobe APP14 marker,   */
+/* component ids 'R','G','B' without JFIF, other samplings, 16-bit quantisation tables, several scans, DNL,       */
+/* a dimension of 0 or above ICAP_JPEG_MAX_DIM, a segment length past the end, a missing EOI, restart markers     */
+/* out of sequence, Huffman tables that are not a prefix code. max_segs < nseg with segs != NULL: ICAP_ERR_ARG.   */
+int icap_jpeg_parse(const uint8_t* data, int64_t size, icap_jpeg_desc* desc, icap_jpeg_segment* segs,
+                    int64_t max_segs);
+/* Host decoder built from the same inline functions as the kernels; for tests, on no product path. out:         */
+/* RGB uint8 [height][width][3]. *status: 0, or the first error of the entropy data (a code that matches no      */
+/* symbol, a run past coefficient 63, a bad segment); out is then unspecified.                                    */
+int icap_jpeg_decode_host(const uint8_t* data, int64_t size, const icap_jpeg_desc* desc,
+                          const icap_jpeg_segment* segs, uint8_t* out, int32_t* status);
+/* n images in three launches (after one that clears status): entropy decode (one lane per segment, one        */
+/* workgroup per image and 64 segments),                                                                        */
+/* dequantise + IDCT (one lane per block), upsample + colour (one lane per pixel). All pointers are device        */
+/* memory. data: the files' bytes, 16-byte aligned, data_bytes a multiple of 16; descs [n]; segs: every image's   */
+/* segments (offsets relative to the image's first byte); layout int64 [n][5] = {data_off, data_len, seg_off      */
+/* (index into segs), work_off (in blocks: coef + work_off * 64, planes + work_off * 64), out_off (bytes into     */
+/* out)}; coef int16 and planes uint8 scratch of sum(blocks) * 64 elements; out: RGB uint8 [height][width][3]     */
+/* per image; status int32 [n], zeroed by the call: 0 or the image's largest error (out is then unspecified).     */
+/* max_segs / max_blocks / max_h / max_w: the largest nseg, blocks, height and width of the n descriptors (they   */
+/* size the grids). stages: ICAP_JPEG_STAGE_ALL, or a mask of single stages (above). Every read of the stream   */
+/* is bounded by data_len and data_bytes, every block index by the descriptor, so malformed entropy data ends  */
+/* in a status word.                                                                                            */
+int icap_jpeg_decode(int32_t n, const uint8_t* data, int64_t data_bytes, const icap_jpeg_desc* descs,
+                     const icap_jpeg_segment* segs, int64_t total_segs, const int64_t* layout, int32_t max_segs,
+                     int32_t max_blocks, int32_t max_h, int32_t max_w, int16_t* coef, uint8_t* planes,
+                     uint8_t* out, int32_t* status, int32_t stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
