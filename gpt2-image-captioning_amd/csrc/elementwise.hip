@@ -359,11 +359,11 @@ __global__ void rows_unpack_kernel(int B, int P, int D, const T* __restrict__ sr
 
 // ---------------------------------------------------------------- cross entropy
 template <typename T>
-__global__ __launch_bounds__(256) void ce_kernel(int64_t V, const T* __restrict__ logits, int64_t ld,
+__global__ __launch_bounds__(256) void ce_kernel(int64_t V, const T* logits, int64_t ld,
                                                 const int32_t* __restrict__ labels,
                                                 const int32_t* __restrict__ n_valid, float* __restrict__ loss_rows,
                                                 T* dlogits, float grad_scale, const int32_t* __restrict__ rows_dev) {
-  __shared__ float redm[4], reds[4];
+  __shared__ float redm[4], reds[4], xy_s;
   const int64_t r = blockIdx.x;
   if (rows_dev && r >= *rows_dev) return;  // compacted targets: this row does not exist
   const int y = labels[r];
@@ -397,13 +397,16 @@ __global__ __launch_bounds__(256) void ce_kernel(int64_t V, const T* __restrict_
   s = (m == -INFINITY) ? 0.f : s * __expf(m - bm);
   s = wave_sum(s);
   if (lane == 0) { redm[w] = bm; reds[w] = s; }
+  // dlogits may alias logits: the label's logit goes to LDS before the barrier and every dlogits store comes after
+  // it (the LDS write needs the loaded value, so the load has landed before any wave can overwrite x[y])
+  if (tid == 0) xy_s = io<T>::ld(x + y);
   __syncthreads();
   float M = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
   float Ssum = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) Ssum += reds[k] * __expf(redm[k] - M);
   const float lse = M + logf(Ssum);
-  if (tid == 0) loss_rows[r] = lse - io<T>::ld(x + y);
+  if (tid == 0) loss_rows[r] = lse - xy_s;
   if (dlogits) {
     const float nv = (float)(*n_valid);
     const float sc = grad_scale / nv;
@@ -430,13 +433,13 @@ __global__ __launch_bounds__(256) void ce_kernel(int64_t V, const T* __restrict_
 // flight together), then the block's online max / sum-exp and the dlogits pass both run from the registers
 // (the two-pass kernel above reads the row twice: r01 PMC 541 MB per launch against 360 MB algorithmic).
 template <int R>
-__global__ __launch_bounds__(512) void ce_bf16_reg_kernel(int64_t V, const bf16_t* __restrict__ logits, int64_t ld,
+__global__ __launch_bounds__(512) void ce_bf16_reg_kernel(int64_t V, const bf16_t* logits, int64_t ld,
                                                          const int32_t* __restrict__ labels,
                                                          const int32_t* __restrict__ n_valid,
                                                          float* __restrict__ loss_rows, bf16_t* dlogits,
                                                          float grad_scale, const int32_t* __restrict__ rows_dev) {
   constexpr int NT = 512, NW = NT / 64;
-  __shared__ float redm[NW], reds[NW];
+  __shared__ float redm[NW], reds[NW], xy_s;
   const int64_t r = blockIdx.x;
   if (rows_dev && r >= *rows_dev) return;
   const int y = labels[r];
@@ -486,6 +489,7 @@ __global__ __launch_bounds__(512) void ce_bf16_reg_kernel(int64_t V, const bf16_
   s = (m == -INFINITY) ? 0.f : s * __expf(m - bm);
   s = wave_sum(s);
   if (lane == 0) { redm[w] = bm; reds[w] = s; }
+  if (tid == 0) xy_s = bf2f(x[y]);  // before the barrier, as in ce_kernel: dlogits may alias logits
   __syncthreads();
   float M = redm[0];
 #pragma unroll
@@ -494,7 +498,7 @@ __global__ __launch_bounds__(512) void ce_bf16_reg_kernel(int64_t V, const bf16_
 #pragma unroll
   for (int k = 0; k < NW; ++k) Ssum += reds[k] * __expf(redm[k] - M);
   const float lse = M + logf(Ssum);
-  if (tid == 0) loss_rows[r] = lse - bf2f(x[y]);
+  if (tid == 0) loss_rows[r] = lse - xy_s;
   if (dlogits) {
     const float sc = grad_scale / (float)(*n_valid);
     bf16_t* dx = dlogits + r * ld;
