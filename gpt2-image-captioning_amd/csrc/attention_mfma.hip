@@ -897,7 +897,10 @@ bool mfma_attention_ok(const icap_attn_args* a, bool bwd) {
   if (a->dtype != ICAP_BF16 || (a->hd != 64 && a->hd != 96) || a->S > 16 * amfma::MAXKT) return false;
   if ((a->ld_qkv & 7) || (bwd && (a->ld_dout & 7))) return false;
   const amfma::Geo g = mfma_geo(a);
-  return (bwd ? mfma_bwd_lds(g) : mfma_fwd_lds(g)) <= 160 * 1024;
+  // backward: mfma_attention_launch runs v2 whenever mfma_bwd2_ok holds, so v1's (larger) LDS image only has to
+  // fit when v1 is what would run (hd 96, S 113..128 with O: v1 needs 165,376 B, bwd2_kernel<96> 115,840 B)
+  if (bwd) return mfma_bwd2_ok(a) || mfma_bwd_lds(g) <= 160 * 1024;
+  return mfma_fwd_lds(g) <= 160 * 1024;
 }
 
 template <typename K>
