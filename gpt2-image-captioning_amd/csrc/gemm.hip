@@ -1,3 +1,5 @@
+#include <cstdlib>
+
 #include "gemm_tile.h"
 #include "gemm_launch.h"
 
@@ -471,11 +473,22 @@ extern "C" int icap_gemm_plan_info(const icap_gemm_args* a, int32_t* splits, int
   return ICAP_OK;
 }
 
+// ICAP_GROUP128=1: icap_gemm_group keeps the 128 x 128 body for every group (A/B runs and the tests that compare the
+// two bodies bit for bit). The one variable the product library reads, at every grouped call and not once, so that one
+// process can run both; a captured graph keeps the body it was captured with.
+static bool group_force128() {
+  const char* e = std::getenv("ICAP_GROUP128");
+  return e != nullptr && std::atoi(e) == 1;
+}
+
 extern "C" int icap_gemm_group(const icap_gemm_args* a, int32_t n, void* stream) {
   ICAP_REQUIRE(a != nullptr && n >= 1 && n <= ICAP_GEMM_GROUP_MAX, "icap_gemm_group: 1 ... 8 products");
+  static_assert(ICAP_GEMM_GROUP_MAX == GROUP_MAX, "the group's planner and its kernel argument hold the same count");
   GemmGroup g;
   g.n = 0;
+  g.swap = 0;
   g.tstart[0] = 0;
+  int64_t Ms[ICAP_GEMM_GROUP_MAX], Ns[ICAP_GEMM_GROUP_MAX];
   for (int i = 0; i < n; ++i) {
     const icap_gemm_args& p = a[i];
     // (the general argument checks of a single unsplit product on the automatic path, then the group's own
@@ -495,15 +508,26 @@ extern "C" int icap_gemm_group(const icap_gemm_args* a, int32_t n, void* stream)
     g.a[k] = p;
     g.a[k].split_k = 1;
     g.a[k].tickets = nullptr;
-    g.tiles_n[k] = (int)((p.N + GBN - 1) / GBN);
-    g.nk[k] = (int)((p.K + 63) / 64);
-    const int64_t tiles = ((p.M + GBM - 1) / GBM) * (int64_t)g.tiles_n[k];
-    ICAP_REQUIRE(g.tstart[k] + tiles < (1ll << 30), "icap_gemm_group: too many tiles");
-    g.tstart[k + 1] = g.tstart[k] + (int)tiles;
+    g.nk[k] = (int)((p.K + 63) / 64) | (gemm_diag() << 28);  // (diagnostic build: ICAP_GEMM_DIAG, as in icap_gemm)
+    Ms[k] = p.M, Ns[k] = p.N;
     ++g.n;
   }
   if (g.n == 0) return ICAP_OK;
-  launch_group_kout(g, (int)device_cus(), reinterpret_cast<hipStream_t>(stream));
+  const int cus = (int)device_cus();
+  const GroupPlan gp = gemm_group_plan(Ms, Ns, g.n, cus, group_force128());
+  ICAP_REQUIRE(gp.total < (1ll << 30), "icap_gemm_group: too many tiles");
+  for (int k = 0; k < g.n; ++k) {
+    if (gp.big && ((gp.swap >> k) & 1)) {  // C^T = B^T A: the narrow operand takes the tile's rows
+      icap_gemm_args& p = g.a[k];
+      std::swap(p.A, p.B);
+      std::swap(p.lda, p.ldb);
+      std::swap(p.M, p.N);
+    }
+    g.tiles_n[k] = gp.tiles_n[k];
+    g.tstart[k + 1] = g.tstart[k] + gp.tiles_m[k] * gp.tiles_n[k];
+  }
+  g.swap = gp.big ? gp.swap : 0u;
+  launch_group_kout(g, cus, gp.big, reinterpret_cast<hipStream_t>(stream));
   return check_launch("icap_gemm_group");
 }
 

@@ -31,8 +31,10 @@ struct GemmGroup {
   int nk[ICAP_GEMM_GROUP_MAX];
   int tstart[ICAP_GEMM_GROUP_MAX + 1];
   int n;
+  unsigned swap;  // (128 x 256 tiles) bit i: a[i] holds the product with A and B exchanged, its tiles store C^T
 };
-void launch_group_kout(const GemmGroup& g, int cus, hipStream_t s);
+// big: the 128 x 256 tiles of gemm_group256_kernel (the host's gemm_group_plan: the group then fits one round)
+void launch_group_kout(const GemmGroup& g, int cus, bool big, hipStream_t s);
 
 // The epilogue kinds a unit holds: the 128-row variants spread theirs over three units (gemm.hip tile_launcher).
 enum KindSet : int { KINDS_PLAIN = 1, KINDS_ACT = 2, KINDS_LN = 4, KINDS_ALL = 7 };

@@ -566,4 +566,23 @@ int gemm_no_instantiation(const GemmPlan& pl) {
   return ICAP_ERR_ARG;
 }
 
+GroupPlan gemm_group_plan(const int64_t* M, const int64_t* N, int n, int cus, bool force128) {
+  GroupPlan big, small;
+  big.big = true;
+  for (int i = 0; i < n && i < GROUP_MAX; ++i) {
+    const bool sw = N[i] <= GROUP_SWAP_N;
+    const int64_t rows = sw ? N[i] : M[i], cols = sw ? M[i] : N[i];
+    const int64_t bm = cdiv(rows, GROUP_BM), bn = cdiv(cols, GROUP_BN_BIG);
+    const int64_t sm = cdiv(M[i], GBM), sn = cdiv(N[i], GBN);
+    // (a product of more tiles than any one round holds only has to keep the sums and the casts in range)
+    const int64_t cap = 1ll << 30;
+    big.tiles_m[i] = (int)(bm < cap ? bm : cap), big.tiles_n[i] = (int)(bn < cap ? bn : cap);
+    small.tiles_m[i] = (int)(sm < cap ? sm : cap), small.tiles_n[i] = (int)(sn < cap ? sn : cap);
+    if (sw) big.swap |= 1u << i;
+    big.total += (bm < cap && bn < cap && bm * bn < cap) ? bm * bn : cap;
+    small.total += (sm < cap && sn < cap && sm * sn < cap) ? sm * sn : cap;
+  }
+  return (!force128 && big.total <= cus) ? big : small;
+}
+
 }  // namespace icap

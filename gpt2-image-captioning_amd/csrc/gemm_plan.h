@@ -172,4 +172,21 @@ const char* gemm_plan_kernel_name(const icap_gemm_args& a, const GemmPlan& pl);
 // ICAP_ERR_ARG for a launch whose form does not exist (tile_form_exists / g8p_form_exists); the error text names it
 int gemm_no_instantiation(const GemmPlan& pl);
 
+// The tile choice of one grouped launch (icap_gemm_group, round 10). A group takes the split-role K-outer body on
+// 128 x 256 tiles (big) when its tiles then fit ONE round of one block per compute unit, total <= cus; otherwise, or
+// with force128 (the ICAP_GROUP128 override), it keeps the 128 x 128 body and walks total tiles on min(total, cus)
+// blocks. On the big tiles a product with at most GROUP_SWAP_N output columns (a bias gradient dY^T . ones) runs with
+// its operands exchanged (swap bit i): the narrow operand on the tile's 128 rows, the wide one on its 256 columns, the
+// tile stored transposed — ceil(M / 256) tiles instead of ceil(M / 128). Every K-outer shape gemm_validate accepts
+// fits either tile (columns past M / N are read and never stored), so the round count is the only condition.
+constexpr int GROUP_MAX = 8, GROUP_BM = 128, GROUP_BN_BIG = 256, GROUP_SWAP_N = 4;
+struct GroupPlan {
+  bool big = false;            // 128 x 256 tiles (gemm_group256_kernel); else 128 x 128 (gemm_group_kernel)
+  unsigned swap = 0;           // bit i: product i runs with A and B exchanged (big only)
+  int tiles_m[GROUP_MAX] = {}, tiles_n[GROUP_MAX] = {};  // per product, of the orientation it runs in
+  int64_t total = 0;           // tiles of the whole group
+};
+// n <= GROUP_MAX products of M[i] x N[i] outputs (all positive)
+GroupPlan gemm_group_plan(const int64_t* M, const int64_t* N, int n, int cus, bool force128);
+
 }  // namespace icap

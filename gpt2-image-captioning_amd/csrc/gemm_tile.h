@@ -54,7 +54,15 @@ namespace icap {
 // stored at chunk ch ^ kout_swz(r) (cdna_hip_programming.md T10 layout (b)) so the transposed reads below are
 // at most 2-way bank conflicted.
 __device__ __forceinline__ int kout_swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ int kout_off(int r, int ch) { return r * 256 + ((ch ^ kout_swz(r)) << 4); }
+// ROWB = 512 (round 10: the 256-column B image of the grouped launch's 128 x 256 tiles): a 512-byte k-row is two
+// spans of the 64 banks, so every row still starts at bank 0 and a chunk's banks are 4 (ch & 15) .. + 3: the swizzle
+// is below 16 and leaves bit 4 of the chunk index (which half of the row) alone, so modulo 16 the physical chunk is
+// what the 256-byte image has and the bank argument of kout_frag carries over unchanged — the two 16-lane groups of a
+// 32-lane half read rows {kb + q} and {kb ^ 8 + q}, q = 0 .. 3, chunk pair 2 m, 2 m + 1: swz(r) = (q << 2) | (r >> 2 & 3)
+// sends the eight (group, q) pairs to the eight distinct chunk pairs (2 m) ^ (q << 2) ^ (2 or 0) modulo 16, 8 pairs x
+// 32 bytes = all 64 banks once. (The LDS-DMA writes the image linearly, 1 KiB = two 512-byte rows per instruction.)
+template <int ROWB = 256>
+__device__ __forceinline__ int kout_off(int r, int ch) { return r * ROWB + ((ch ^ kout_swz(r)) << 4); }
 typedef short kv4s_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) kv4s_t* kout_lds_ptr;
 // MFMA 16x16x32 operand (lane: column c0 + (lane & 15)) over k-rows r0..r0+31 of a K-outer image, as two
@@ -64,12 +72,13 @@ typedef __attribute__((address_space(3))) kv4s_t* kout_lds_ptr;
 // in the same columns, which the image's XOR makes conflict-free (cdna_hip_programming.md T10); with adjacent
 // blocks (kb = 4g) every read was 2-way (SQ_LDS_BANK_CONFLICT = 0.47 of the kernel's LDS cycles,
 // profiles/r04_pmc_lds.txt). Any k order works as long as both operands use the same one.
+template <int ROWB = 256>
 __device__ __forceinline__ uint4 kout_frag(const char* img, int r0, int c0, int lane) {
   const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
   const int ch = (c0 >> 3) + (pp >> 1), half = (pp & 1) * 8;
   const int kb = 8 * (g & 1) + 4 * (g >> 1);
-  const char* a0 = img + kout_off(r0 + kb + q, ch) + half;
-  const char* a1 = img + kout_off(r0 + 16 + kb + q, ch) + half;
+  const char* a0 = img + kout_off<ROWB>(r0 + kb + q, ch) + half;
+  const char* a1 = img + kout_off<ROWB>(r0 + 16 + kb + q, ch) + half;
   const kv4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((kout_lds_ptr)(a0));
   const kv4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((kout_lds_ptr)(a1));
   uint4 r;
@@ -131,14 +140,18 @@ template <typename TI, typename TC, int NST, int MINB, int WM, int WN, int TM, i
 // The body of one tile (gemm_kernel below runs it once per block, or, for ROLES, once per live tile of a grid-stride
 // loop): bid = the tile's block id in the capacity grid of tiles_m x tiles_n x splits blocks, Mv = the device row count.
 __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int splits, int nk_split, uint32_t drop_thresh,
-                                          float inv_keep, const int bid, const int tiles_m, const int64_t Mv) {
-  static_assert(!KOUT || (sizeof(TI) == 2 && 16 * WM * TM == 128 && 16 * WN * TN == 128),
-                "K-outer operands: bf16, 128 x 128 tiles");
+                                          float inv_keep, const int bid, const int tiles_m, const int64_t Mv,
+                                          const bool tstore = false) {
+  // (round 10: K-outer 128 x 256 tiles exist for the split-role body of the grouped launch only, gemm_group256_kernel)
+  static_assert(!KOUT || (sizeof(TI) == 2 && 16 * WM * TM == 128 &&
+                          (16 * WN * TN == 128 || (ROLES && 16 * WN * TN == 256 && TN == 4))),
+                "K-outer operands: bf16, 128 x 128 tiles (split roles: or 128 x 256 of 8 MFMA waves)");
   static_assert(!ROLES || (sizeof(TI) == 2 && MINB == 1 &&
                             ((WM == 2 && WN == 2 && NST >= 3 && (!KOUT || (TM == 4 && TN == 4))) ||
+                             (KOUT && WM == 2 && WN == 4 && TM == 4 && TN == 4 && NST >= 3) ||
                              (!KOUT && WM * WN == 8 && NST >= 2))),
                 "roles: bf16 operands, 4 MFMA waves on a ring of >= 3 stages (K-outer: 128 x 128 tiles) or 8 on >= 2 "
-                "(row-major), one block per CU");
+                "(row-major; K-outer: 128 x 256 tiles on >= 3), one block per CU");
   // MX block-scaled fp8 (TI = fp8_t): a stage's 128-byte LDS row is one 128-deep K step of
   // v_mfma_scale_f32_16x16x128_f8f6f4 (twice the bf16 flops per staged byte and per fragment byte read); the
   // per-32 E8M0 scales of the wave's 4 fragment rows of A and of B come in one 16-byte load each per stage
@@ -483,8 +496,16 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
         if constexpr (KOUT) {
           // K-outer (round 6): 4 k-rows of 256 B per piece, lane l -> k-row 4 q' + (l >> 4), physical chunk l & 15
           // holding logical chunk (l & 15) ^ kout_swz(row) (the tile kernel's T10 (b) image)
-          const int krow = (i < PA ? q : q - BM / 8) * 4 + (lane >> 4);
-          voff[i] = (uint32_t)((int64_t)krow * (i < PA ? p.lda : p.ldb) + (((lane & 15) ^ kout_swz(krow)) << 3)) * ES;
+          // (round 10, B image of 256 columns: 2 k-rows of 512 B per piece, lane l -> k-row 2 q' + (l >> 5), physical
+          // chunk l & 31 holding logical chunk (l & 31) ^ kout_swz(row))
+          constexpr int BLPR = BN / 8;  // lanes (16-byte chunks) per k-row of the B image
+          if (i < PA || BLPR == 16) {
+            const int krow = (i < PA ? q : q - BM / 8) * 4 + (lane >> 4);
+            voff[i] = (uint32_t)((int64_t)krow * (i < PA ? p.lda : p.ldb) + (((lane & 15) ^ kout_swz(krow)) << 3)) * ES;
+          } else {
+            const int krow = (q - BM / 8) * (64 / BLPR) + lane / BLPR;
+            voff[i] = (uint32_t)((int64_t)krow * p.ldb + (((lane & (BLPR - 1)) ^ kout_swz(krow)) << 3)) * ES;
+          }
         } else {
           const int row = (i < PA ? q : q - BM / 8) * 8 + lrow;  // 8-row piece
           voff[i] = (uint32_t)((int64_t)row * (i < PA ? p.lda : p.ldb) + lchunk) * ES;
@@ -568,8 +589,53 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
         for (int i = 0; i < TM; ++i) fa[i] = __builtin_bit_cast(u32x4_t, kout_frag(As, ks * 32, wm * 16 * TM + i * 16, lane));
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          fb[j] = __builtin_bit_cast(u32x4_t, kout_frag(As + BM * GROWB, ks * 32, wn * 16 * TN + j * 16, lane));
+          fb[j] = __builtin_bit_cast(u32x4_t, kout_frag<2 * BN>(As + BM * GROWB, ks * 32, wn * 16 * TN + j * 16, lane));
       };
+      // (round 10, the 128 x 256 tiles: hipcc hoists every fragment address of kout_frag out of the k loop, one
+      // register each — measured on a first form of 4 MFMA waves of 64 x 128, whose 128 accumulator + 96 fragment
+      // registers left no room for 12 of them: 25 registers spilled. The address of fragment i is stage + lane row +
+      // ((lane chunk ^ swizzle) ^ 2 i) << 4: the fragment index sits in chunk bits the swizzle also flips, so it is an
+      // XOR, not an immediate offset. Two XOR bases and two row offsets stay live (made opaque per call, so nothing
+      // derived from them is loop-invariant) and each fragment costs one XOR and one add; the second read of a
+      // fragment, 16 k-rows on, has the same swizzle.)
+      const int kq = 8 * (fg & 1) + 4 * (fg >> 1) + ((lane >> 2) & 3);  // this lane's k-row within a 16-row block
+      uint32_t xa = (uint32_t)(((wm * 2 * TM + ((lane & 3) >> 1)) ^ kout_swz(kq)) << 4);
+      uint32_t xb = (uint32_t)(((wn * 2 * TN + ((lane & 3) >> 1)) ^ kout_swz(kq)) << 4);
+      const uint32_t ra = (uint32_t)(kq * 2 * BM + (lane & 1) * 8);
+      const uint32_t rbb = (uint32_t)(BM * GROWB + kq * 2 * BN + (lane & 1) * 8);
+      auto rdk8 = [&](uint32_t sb, int ks, u32x4_t(&fa)[TM], u32x4_t(&fb)[TN]) __attribute__((always_inline)) {
+        asm volatile("" : "+v"(xa), "+v"(xb));
+        const uint32_t ba = sb + ra + (uint32_t)(ks * 32 * 2 * BM), bb = sb + rbb + (uint32_t)(ks * 32 * 2 * BN);
+        auto frag = [&](uint32_t a0, uint32_t step16) __attribute__((always_inline)) {
+          const kv4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((kout_lds_ptr)(uintptr_t)a0);
+          const kv4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((kout_lds_ptr)(uintptr_t)(a0 + step16));
+          u32x4_t r;
+          r.x = (uint32_t)(uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
+          r.y = (uint32_t)(uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
+          r.z = (uint32_t)(uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
+          r.w = (uint32_t)(uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
+          return r;
+        };
+#pragma unroll
+        for (int i = 0; i < TM; ++i) fa[i] = frag(ba + (xa ^ (uint32_t)(i << 5)), 16 * 2 * BM);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) fb[j] = frag(bb + (xb ^ (uint32_t)(j << 5)), 16 * 2 * BN);
+      };
+      if constexpr (BN == 256) {
+        rdk8(sbase, 0, fa0, fb0);
+        for (int kt = 0; kt < nk; ++kt) {
+          const uint32_t sb = sbase + (uint32_t)((kt % NST) * STB);
+          retire(fa0, fb0);
+          rdk8(sb, 1, fa1, fb1);
+          mm(fa0, fb0);
+          retire(fa1, fb1);
+          __builtin_amdgcn_s_barrier();  // B_{kt+1}
+          __builtin_amdgcn_sched_barrier(0);
+          if (kt + 1 < nk) rdk8(sbase + (uint32_t)(((kt + 1) % NST) * STB), 0, fa0, fb0);
+          mm(fa1, fb1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
       rdk(sbase, 0, fa0, fb0);
       for (int kt = 0; kt < nk; ++kt) {
         const uint32_t sb = sbase + (uint32_t)((kt % NST) * STB);
@@ -582,6 +648,7 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
         if (kt + 1 < nk) rdk(sbase + (uint32_t)(((kt + 1) % NST) * STB), 0, fa0, fb0);
         mm(fa1, fb1);
         __builtin_amdgcn_sched_barrier(0);
+      }
       }
     } else if constexpr (NW == 8) {
       // two MFMA waves per SIMD (variant 28, 96 x 64 per wave): one fragment set each (the 168-register budget of
@@ -760,6 +827,37 @@ __device__ __forceinline__ void gemm_body(icap_gemm_args p, int tiles_n, int spl
   // Nobody waits on a block that has not taken its ticket, so there is no residency assumption
   // (cdna_hip_programming.md §5 "In-launch split-K reduction", §6 Guideline 16 R1 with sc1 loads).
   ICAP_STAMP(3, ICAP_NOW());
+  if constexpr (KOUT && ROLES && BN == 256) {
+    // round 10, the grouped launch's bias sums: a product with at most 4 output columns (db = dY^T . ones) runs with
+    // its operands exchanged — the narrow one on the 128 rows, dY on the 256 columns — so its tile holds C^T: element
+    // (row, col) of the tile belongs at C[col][row] (p.ldc is C's own leading dimension). The products a b and b a and
+    // the MFMA's order over k are the same, so each sum has the bits of the product run the natural way round. Rows
+    // 0 .. 3 of the tile are the registers v of accumulator row 0 in lanes 0 .. 15 of the wm == 0 waves; the same
+    // arithmetic as epiw's scalar path: fma(alpha, acc, 0), then + beta C.
+    if (tstore) {
+      if (wave < NW && wm == 0 && fg == 0) {
+        float* C = reinterpret_cast<float*>(p.C);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int64_t c = n0 + wn * 16 * TN + j * 16 + fr;
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            if (m0 + v < Mv && c < N) {
+              float x[1] = {acc[0][j][v]}, a1[1];
+              const float b0[1] = {0.f};
+              epi_fwd_act<1, ACT_OFF>(p, x, b0, a1);
+              float* cp = C + c * p.ldc + (m0 + v);
+              *cp = p.beta != 0.f ? x[0] + p.beta * *cp : x[0];
+            }
+          }
+        }
+      }
+      ICAP_STAMP(0, (uint64_t)tile << 32);
+      ICAP_STAMP(4, ICAP_NOW());
+      ICAP_STAMP(5, ICAP_NOW());
+      return;
+    }
+  }
   const bool fused = !ROLES && splits > 1 && p.tickets != nullptr;  // (roles: one K range per tile, host rule)
   if (fused) {
     typedef uint32_t u32x4f_t __attribute__((ext_vector_type(4)));

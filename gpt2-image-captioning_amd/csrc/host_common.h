@@ -4,8 +4,9 @@
 #pragma once
 
 // Diagnostic build only (make stamps: -DICAP_STAMPS): A/B overrides of the kernel choice read from the process
-// environment (tools/ab). The product library reads no environment variable: in it every choice is a function of
-// the call's arguments and diag_env returns its default at compile time.
+// environment (tools/ab). The product library reads one environment variable, ICAP_GROUP128 (gemm.hip: the grouped
+// launch's 128 x 128 body, for A/B runs and the bitwise tests); every other choice in it is a function of the call's
+// arguments and diag_env returns its default at compile time.
 #ifdef ICAP_STAMPS
 #include <cstdlib>
 static inline int diag_env(const char* name, int dflt) {

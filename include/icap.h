@@ -187,7 +187,12 @@ int icap_gemm(const icap_gemm_args* a, void* stream);
 /* of n (1 ... 8) K-outer products a[0 .. n-1] (trans_ab, bf16 A / B, fp32 C, alpha / beta, no epilogue        */
 /* operands, no m_dev) in ONE launch, each unsplit on the split-role K-outer kernel (path 11's body): no split-K */
 /* slabs, no reduce pass, the group's tiles filling the chip together. Bitwise what icap_gemm gives each with   */
-/* split_k = 1 and path 11; products with M or N = 0 are skipped.                                              */
+/* split_k = 1 and path 11; products with M or N = 0 are skipped. Every other product needs K > 0              */
+/* (ICAP_ERR_ARG otherwise: unlike icap_gemm, the group does not run the beta-only update C = beta C of an      */
+/* empty sum). A group whose 128 x 256 tiles fit one round of one block per compute unit runs on those tiles    */
+/* (products of at most 4 output columns, the bias sums against a ones column, with their operands exchanged);  */
+/* any other group, and every group while the environment holds ICAP_GROUP128=1 (looked up at each call), on    */
+/* 128 x 128 tiles. The bits are the same either way.                                                           */
 int icap_gemm_group(const icap_gemm_args* a, int32_t n, void* stream);
 
 /* ------------------------------------------------------------------------- */
