@@ -15,14 +15,14 @@ from .clip_text import (CLIPTextConfig, CLIPTextTower, ClipTextCore, chunk_capti
                         load_clip_text_model, load_image_embeddings_file_names, map_caption_id_to_caption)
 from .jpeg import DeviceJpegDecoder, decode_jpeg, parse_jpeg  # noqa: E402,F401
 from .dataset import CocoDataset, SyntheticCaptionDataset  # noqa: E402,F401
-from .engine import CaptionTrainer  # noqa: E402,F401
+from .engine import CaptionScorer, CaptionTrainer  # noqa: E402,F401
 from .gpt2 import GPT2Config, GPT2LMHeadModel  # noqa: E402,F401
 from .mapper import MLPMappingNetwork, TransformerMappingNetwork  # noqa: E402,F401
 from .models import (ImageCaptioningModel, RetrievalAggregator, RetrievalAugmentedTransformer,  # noqa: E402,F401
                      load_gpt2_tokenizer)
 from .retrieval import (DeviceRetrievalStore, build_retrieval_store, create_retrieval_store,  # noqa: E402,F401
                         save_retrieval_store)
-from .evaluate import evaluate_rat_epoch, generate_and_evaluate_rat  # noqa: E402,F401
+from .evaluate import evaluate_loss, evaluate_rat_epoch, generate_and_evaluate_rat  # noqa: E402,F401
 from .train import train, train_rat  # noqa: E402,F401
 from .vit import ViTConfig, ViTImageTower, extract_vit_embedding_from_image, extract_vit_embeddings, load_vit_model  # noqa: E402,F401
 from .dino import (DINOv3ImageTower, DinoConfig, extract_dino_embeddings, get_dinov3_preprocessor,  # noqa: E402,F401

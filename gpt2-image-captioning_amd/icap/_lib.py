@@ -180,6 +180,10 @@ SIGNATURES = {
     "icap_rows_unpack": (C.c_int, [i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
     "icap_cross_entropy_workspace_bytes": (sz, [i64]),
     "icap_cross_entropy": (C.c_int, [i32, i64, i64, vp, i64, vp, vp, vp, vp, f32, vp, vp, vp]),
+    "icap_caption_score_workspace_bytes": (sz, [i64]),
+    "icap_caption_score": (C.c_int, [i32, i64, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp,
+                                     vp, vp, vp]),
+    "icap_caption_target_ranges": (C.c_int, [i32, i32, vp, vp, vp, vp, vp]),
     "icap_adamw_workspace_bytes": (sz, [i64]),
     "icap_adamw_step": (C.c_int, [C.POINTER(AdamWArgs), vp, vp]),
     "icap_sqnorm": (C.c_int, [i64, vp, vp, vp, vp]),

@@ -517,6 +517,121 @@ class CaptionTrainer:
         return self.gws.loss
 
 
+class CaptionScorer:
+    """Teacher-forced scoring of a batch of captions, the forward-only sibling of CaptionTrainer: mapper forward ->
+    GPT-2 forward (dropout off) on packed token rows -> LM head on the target rows -> icap_caption_target_ranges ->
+    icap_caption_score. Inputs and outputs live in fixed device buffers:
+
+        nll [B] fp32, n_tokens [B] int32, n_correct [B] int32, token_logprobs [B, Lc] fp32   (of the last run)
+        totals float64 [3]: sum nll, sum n_tokens, sum n_correct over every run since reset()
+
+    run() allocates nothing and never synchronises with the host; with use_graph its first call runs eagerly (warm-up)
+    and later calls replay one captured HIP graph. Eager and replay give the same bits (icap_caption_score has no
+    atomics). total loss = totals[0] / totals[1] is the reference's loss (src/models.py:286-325) over everything
+    scored. Works in fp32 parity mode, bf16 (folded-LayerNorm forward) and with the fp8 GPT-2 products, both mappers,
+    with or without a task prefix; the image embeddings of a retrieval-augmented model are augmented by the caller."""
+
+    def __init__(self, model, batch_size: int, caption_len: int, *, compact_head: bool = True, pack_rows: bool = True):
+        self.model = model
+        self.dtype = model.compute_dtype
+        self.B, self.Lc = batch_size, caption_len
+        self.dev = model.device
+        B, Lc = batch_size, caption_len
+        flat = model.flat()
+        self.mcore = model.mapping_network.core(self.dtype, flat)
+        self.gcore = model._gcore()
+        P = model.total_prefix_length
+        self.P = P
+        self.mws = self.mcore.alloc(B, train=False)
+        self.gws = self.gcore.alloc_train(B, P, Lc, compact_head=compact_head, pack=pack_rows, backward=False)
+        D, E = self.gcore.D, self.mcore.E
+        dev = self.dev
+        if model.task_prefix_embeds is not None:
+            self.pre = torch.empty((B, P, D), dtype=self.dtype, device=dev)
+        self.ids = torch.zeros((B, Lc), dtype=torch.int64, device=dev)
+        self.mask = torch.ones((B, Lc), dtype=torch.int64, device=dev)
+        self.labels = torch.full((B, Lc), -100, dtype=torch.int64, device=dev)
+        self.emb = torch.zeros((B, E), dtype=torch.float32, device=dev)
+        self.emb_c = torch.zeros((B, E), dtype=self.dtype, device=dev)
+        self.ranges = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        self.nll = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.n_tokens = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.n_correct = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.token_logprobs = torch.zeros((B, Lc), dtype=torch.float32, device=dev)
+        self.totals = torch.zeros(3, dtype=torch.float64, device=dev)
+        self.score_ws = torch.empty(ops.caption_score_workspace(self.gws.Mh), dtype=torch.uint8, device=dev)
+        self.gdr = self.gcore.drops(False, 0, None, self.gws.M, B, self.gws.S)
+        self.mdr = self.mcore.drops(False, 0.0, 0, None, B)
+        self.graph = None
+        self._graph_short = False  # the short-sequence flag the graph was captured under
+        self._eager_runs = 0
+
+    def reset(self) -> None:
+        self.totals.zero_()
+
+    def load_batch(self, ids: Tensor, mask: Optional[Tensor], labels: Tensor, emb: Tensor) -> None:
+        """Copy one batch into the fixed buffers (asynchronously from pinned or device memory). mask None: all ones."""
+        if self.gws.pack and self.gws.live_rows_hint is None and labels.device.type == "cpu":
+            # the first host batch's packed row count: the GEMM kernel choice for the expected live rows, as in
+            # CaptionTrainer.load_batch (device labels: no hint, rather than a device-to-host sync)
+            self.gws.live_rows_hint = live_rows(labels, self.P)
+            self.gws.seq_sq_hint = live_rows(labels, self.P, squares=True)
+        if self.gws.pack and SHORT_ONLY:
+            # as CaptionTrainer.load_batch: a guarantee read from host labels only (no device-to-host sync)
+            self.gws.short_only = labels.device.type == "cpu" and max_seq_len(labels, self.P) <= 32
+        self.ids.copy_(ids, non_blocking=_async_src(ids))
+        if mask is None:
+            self.mask.fill_(1)
+        else:
+            self.mask.copy_(mask, non_blocking=_async_src(mask))
+        self.labels.copy_(labels, non_blocking=_async_src(labels))
+        self.emb.copy_(emb, non_blocking=_async_src(emb))
+
+    def _schedule(self) -> None:
+        B, P, Lc, D = self.B, self.P, self.Lc, self.gcore.D
+        model, mc, gc, ws = self.model, self.mcore, self.gcore, self.gws
+        ops.convert(self.emb, self.emb_c)
+        mc.forward(self.mws, self.emb_c, self.mdr, train=False)
+        pre, pbs = mc.prefix_view(self.mws)
+        if model.task_prefix_embeds is not None:  # [image prefix ; task prefix] (src/models.py:269-283)
+            Pm = mc.P
+            ops.convert(_rows_view(pre, B, Pm * D, pbs), self.pre.view(B, P * D)[:, : Pm * D])
+            ops.broadcast_rows(model.task_prefix_embeds.data, self.pre.view(-1)[Pm * D:], B, P * D)
+            pre, pbs = self.pre, P * D
+        gc.forward_train(ws, pre, pbs, self.ids, self.mask, self.labels, self.gdr, fuse_dlogits=False, ce=False)
+        cp = ws.compact
+        slot = ws.row_slot if cp else None
+        ops.caption_target_ranges(B, ws.S, self.ranges, row_slot=slot, seqs=ws.seqs)
+        ops.caption_score(ws.logits, gc.V, ws.labels_c if cp else ws.labels_shift, self.ranges, self.nll,
+                          self.n_tokens, self.n_correct, self.score_ws, rows=ws.Mh,
+                          rows_dev=ws.n_valid if cp else None, token_logprobs=self.token_logprobs, P=P, Lc=Lc,
+                          row_slot=slot, seqs=ws.seqs, totals=self.totals)
+
+    @torch.no_grad()
+    def run(self, use_graph: bool = True) -> None:
+        """Score the loaded batch; the results are in nll / n_tokens / n_correct / token_logprobs, and added to
+        totals. One graph per instance: a graph captured while every sequence was short (packed attention's
+        short-sequence pass only) is replaced, once, by the two-pass form when a longer batch arrives; the two-pass
+        graph serves every batch."""
+        self.model.sync_compute_copies()
+        if not (use_graph and self._eager_runs >= 1):
+            self._schedule()
+            self._eager_runs += 1
+            return
+        so = bool(self.gws.short_only)
+        if self.graph is None or (self._graph_short and not so):
+            torch.cuda.synchronize(self.dev)
+            g = torch.cuda.CUDAGraph()
+            with ops.graph_capture(g):
+                self._schedule()
+            self.graph, self._graph_short = g, so
+        self.graph.replay()
+
+    def loss_tensor(self) -> Tensor:
+        """totals[0] / totals[1] on the device (float64 scalar; NaN before anything was scored)."""
+        return self.totals[0] / self.totals[1]
+
+
 @torch.no_grad()
 def max_seq_len(labels: Tensor, P: int) -> int:
     """The longest packed sequence of a batch (icap_caption_pack's seq_len, restated on the host side of the copy)."""

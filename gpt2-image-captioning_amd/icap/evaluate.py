@@ -123,6 +123,59 @@ def evaluate_rat_epoch(model, db_store, top_k: int, top_i: int, dataset, annotat
     return m
 
 
+LOSS_KEYS = ("val_loss", "val_perplexity", "val_token_accuracy")
+
+
+@torch.no_grad()
+def evaluate_loss(model, dataset, batch_size: int = 128, num_workers: int = 4, device=None, rat=None,
+                  use_graph: bool = True) -> Dict[str, Any]:
+    """Teacher-forced validation loss over EVERY caption of `dataset` (not one per image): the reference's loss
+    (src/models.py:286-325), i.e. sum of the captions' nll over the number of target tokens, its exponential and the
+    share of targets whose label is the argmax of the logits. One engine.CaptionScorer per batch shape (a short last
+    batch gets its own), running totals on the device, one host read at the end. rat: (db_store, top_k, top_i) for a
+    RetrievalAugmentedTransformer."""
+    import math
+
+    from torch.utils.data import DataLoader
+
+    from .engine import CaptionScorer
+    from .train import _collate
+
+    device = device or model.device
+    was_training = model.training
+    model.eval()
+    dl = DataLoader(dataset, batch_size=batch_size, shuffle=False, num_workers=num_workers, collate_fn=_collate,
+                    pin_memory=True, drop_last=False)
+    scorers: Dict[Any, Any] = {}
+    totals = torch.zeros(3, dtype=torch.float64, device=device)
+    aug_out: Dict[int, torch.Tensor] = {}
+    n_caps = 0
+    for batch in dl:
+        ids, mask, labels, emb = batch["token_ids"], batch["attention_mask"], batch["labels"], batch["image_embedding"]
+        B, Lc = ids.shape
+        sc = scorers.get((B, Lc))
+        if sc is None:
+            sc = scorers[(B, Lc)] = CaptionScorer(model, B, Lc)
+            sc.totals = totals  # every shape adds to the same running totals
+        if rat is not None:
+            if B not in aug_out:
+                aug_out[B] = torch.empty((B, emb.shape[1]), dtype=torch.float32, device=device)
+            emb = model.augment(rat[0], emb.to(device, non_blocking=True), rat[2], rat[1], out=aug_out[B])
+        sc.load_batch(ids, mask, labels, emb)
+        sc.run(use_graph=use_graph)
+        n_caps += B
+    t = totals.cpu().tolist()  # the one host read
+    model.train(was_training)
+    nll, ntok, nhit = t[0], int(round(t[1])), int(round(t[2]))
+    loss = nll / ntok if ntok else float("nan")
+    try:
+        ppl = math.exp(loss)
+    except OverflowError:
+        ppl = float("inf")
+    return {"val_loss": loss, "val_perplexity": ppl, "val_token_accuracy": nhit / ntok if ntok else float("nan"),
+            "num_captions": n_caps, "num_tokens": ntok}
+
+
 def save_eval_summary(all_metrics, output_path: str) -> None:
     """src/eval.py:479-491: the per-epoch validation dicts ({"epoch", "loss", **metrics}) as one JSON list."""
     with open(output_path, "w") as f:

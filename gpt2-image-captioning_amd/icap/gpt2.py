@@ -381,7 +381,7 @@ class GPT2Core:
 
     # -- workspaces --------------------------------------------------------------------------------------
     def alloc_train(self, B: int, P: int, Lc: int, keep_for_dw: bool = False,
-                    compact_head: bool = False, pack: bool = False) -> SimpleNamespace:
+                    compact_head: bool = False, pack: bool = False, backward: bool = True) -> SimpleNamespace:
         """compact_head: the LM head and CE run on the rows whose shifted label is not -100 only (at most B*Lc;
         the count lives on the device). The loss ignores every other row (HF/loss/loss_utils.py:32-46,
         ignore_index=-100), so their logits feed nothing and their dlogits are exactly 0: loss and gradients are
@@ -389,7 +389,9 @@ class GPT2Core:
         pack (with compact_head): the blocks run on packed token rows — each sequence's prefix and caption
         positions up to its last loss target (icap_caption_pack), the rest of the [B, P + Lc] grid is dead under
         the causal mask — so every block GEMM, LayerNorm and attention launch covers the live rows only (row
-        count on the device; launches sized for the padded grid, so one captured graph serves every batch)."""
+        count on the device; launches sized for the padded grid, so one captured graph serves every batch).
+        backward=False: a forward-only workspace (engine.CaptionScorer) — none of the backward scratch (dx, dx2, dxd,
+        dff, dqkv, do, da, dhf, the packed d_emb, the fp8 dlogits operand) is allocated."""
         S = P + Lc
         M = B * S
         D, H, dt, dev = self.D, self.H, self.dtype, self.dev
@@ -409,7 +411,8 @@ class GPT2Core:
             ws.seq_len = e(B, dtype=torch.int32)
             ws.m_live = e(1, dtype=torch.int32)
             ws.seqs = (ws.seq_off, ws.seq_len)
-            ws.d_emb = e(M, D)  # the prefix rows' gradient back in the padded [B, S, D] layout
+            if backward:
+                ws.d_emb = e(M, D)  # the prefix rows' gradient back in the padded [B, S, D] layout
         ws.x = [e(M, D) for _ in range(nl + 1)]
         ws.h1 = [e(M, D) for _ in range(nl)]
         ws.qkv = [e(M, 3 * D) for _ in range(nl)]
@@ -444,17 +447,19 @@ class GPT2Core:
         ws.n_valid = e(1, dtype=torch.int32)
         ws.loss = e(1, dtype=torch.float32)
         ws.ce_ws = e(ops.cross_entropy_workspace(Mh), dtype=torch.uint8)
-        # backward scratch
-        ws.dx, ws.dx2, ws.dxd = e(M, D), e(M, D), e(M, D)
-        ws.dff = e(M, 4 * D)
-        ws.dqkv = e(M, 3 * D)
-        ws.do, ws.da = e(M, D), e(M, D)
-        ws.dhf = e(Mh, D)
+        if backward:  # backward scratch
+            ws.dx, ws.dx2, ws.dxd = e(M, D), e(M, D), e(M, D)
+            ws.dff = e(M, 4 * D)
+            ws.dqkv = e(M, 3 * D)
+            ws.do, ws.da = e(M, D), e(M, D)
+            ws.dhf = e(Mh, D)
         ws.qD = ws.q3D = ws.q4D = ws.qhf = ws.qdl = None
         if self.fp8:  # MX operand buffers (each product quantises its activation operand into one of these)
             mx = lambda R, K: ops.MXTensor.empty(R, K, dev)  # noqa: E731
             ws.qD, ws.q3D, ws.q4D = mx(M, D), mx(M, 3 * D), mx(M, 4 * D)
-            ws.qhf, ws.qdl = mx(Mh, D), mx(Mh, self.Vp)
+            ws.qhf = mx(Mh, D)
+            if backward:
+                ws.qdl = mx(Mh, self.Vp)
         return ws
 
     def _fold_train(self, keep_for_dw: bool) -> bool:
@@ -503,9 +508,10 @@ class GPT2Core:
     # -- training forward ------------------------------------------------------------------------------------
     def forward_train(self, ws, prefix: Tensor, prefix_bstride: int, ids: Tensor, mask: Optional[Tensor],
                       labels: Optional[Tensor], dr, fuse_dlogits: bool, grad_scale: float = 1.0,
-                      dlogits: Optional[Tensor] = None) -> None:
+                      dlogits: Optional[Tensor] = None, ce: bool = True) -> None:
         """Embeddings -> 12 blocks -> ln_f -> LM head -> CE (modeling_gpt2.py:514-725 + loss_utils.py:49-71).
-        With fuse_dlogits the CE kernel also writes dlogits (in place over the logits, or into `dlogits`)."""
+        With fuse_dlogits the CE kernel also writes dlogits (in place over the logits, or into `dlogits`).
+        ce=False stops after the LM head (engine.CaptionScorer reads the logits itself)."""
         B, P, Lc, S, M = ws.B, ws.P, ws.Lc, ws.S, ws.M
         D, H, hd = self.D, self.H, self.hd
         cp = ws.compact
@@ -525,7 +531,7 @@ class GPT2Core:
         rows = ws.head_rows_hint if (cp and ws.head_rows_hint is not None) else ws.Mh
         self._mm(ws.hf, ws.qhf, self.wte, getattr(self, "qwte", None), ws.logits, rows_dev=ws.n_valid if cp else None,
                  M=ws.Mh, m_dev=ws.n_valid if cp else None, alg_flops=2.0 * rows * self.V * self.D)
-        if labels is not None:
+        if labels is not None and ce:
             dl = (dlogits if dlogits is not None else ws.logits) if fuse_dlogits else None
             ops.cross_entropy(ws.logits, self.V, ws.labels_c if cp else ws.labels_shift, ws.n_valid, ws.loss, dl,
                               ws.ce_ws, grad_scale, rows=ws.Mh, rows_dev=ws.n_valid if cp else None)

@@ -71,6 +71,7 @@ class ImageCaptioningModel(nn.Module):
         self._flat: Optional[FlatParams] = None
         self._synced_version = None
         self._fwd_cache = {}
+        self._scorers = {}
 
     # -- storage ------------------------------------------------------------------------------------------------
     @property
@@ -194,6 +195,43 @@ class ImageCaptioningModel(nn.Module):
         else:
             mc.backward_from(d_pre[:, : Pm * D], S * D, st.mws, st.emb_c, mg, dwh)
         return [g.clone() for g in flat.grad_views]
+
+    # -- scoring ------------------------------------------------------------------------------------------------
+    def _scorer(self, B: int, Lc: int):
+        """The CaptionScorer of this batch shape (kept while GPT-2 is frozen: its cores are the model's own, which
+        the fused optimizer updates in place; a trained GPT-2 gets a fresh core, so a fresh scorer, per call)."""
+        from .engine import CaptionScorer
+
+        if not self.freeze_gpt_weights:
+            return CaptionScorer(self, B, Lc)
+        key = (B, Lc, self.compute_dtype, self.device, id(self._flat))
+        sc = self._scorers.get(key)
+        if sc is None:
+            sc = self._scorers[key] = CaptionScorer(self, B, Lc)
+        return sc
+
+    @torch.no_grad()
+    def score_captions(self, caption_token_ids: Tensor, image_embeddings: Tensor,
+                       attention_mask: Optional[Tensor] = None, labels: Optional[Tensor] = None, *,
+                       return_token_logprobs: bool = False):
+        """Teacher-forced score of each caption given its image: the loss of forward() (src/models.py:286-325) taken
+        apart per caption, with dropout off. labels None: the ids where attention_mask == 1 (every id without a
+        mask), -100 elsewhere. Returns device tensors nll [B] fp32 (sum over the caption's targets of
+        logsumexp(logits) - logit[label]), logprob = -nll, n_tokens [B] int32, n_correct [B] int32 (targets whose
+        label is the first maximum of the logits) and, on request, token_logprobs [B, Lc] fp32 (0 where a token has
+        no label). sum(nll) / sum(n_tokens) is forward()'s loss. No host synchronisation."""
+        self.sync_compute_copies()
+        B, Lc = caption_token_ids.shape
+        if labels is None:
+            labels = labels_from_mask(caption_token_ids, attention_mask)
+        sc = self._scorer(B, Lc)
+        sc.load_batch(caption_token_ids, attention_mask, labels, image_embeddings)
+        sc.run(use_graph=False)
+        out = SimpleNamespace(nll=sc.nll.clone(), n_tokens=sc.n_tokens.clone(), n_correct=sc.n_correct.clone())
+        out.logprob = -out.nll
+        if return_token_logprobs:
+            out.token_logprobs = sc.token_logprobs.clone()
+        return out
 
     def _gpt_grads(self, flat):
         t = self.gpt.transformer
@@ -340,6 +378,15 @@ class RetrievalAugmentedTransformer(ImageCaptioningModel):
                                attention_mask=attention_mask, labels=labels)
 
     @torch.no_grad()
+    def score_captions(self, db_store, top_i: int, top_k: int, caption_token_ids: Tensor, image_embeddings: Tensor,
+                       attention_mask: Optional[Tensor] = None, labels: Optional[Tensor] = None, *,
+                       return_token_logprobs: bool = False):
+        """ImageCaptioningModel.score_captions on the augmented embeddings (argument order of forward)."""
+        aug = self.augment(db_store, image_embeddings, top_i, top_k)
+        return super().score_captions(caption_token_ids, aug, attention_mask, labels,
+                                      return_token_logprobs=return_token_logprobs)
+
+    @torch.no_grad()
     def generate(self, db_store, top_k: int, top_i: int, image_embeddings: Tensor, max_length: int = 50,
                  temperature: float = 1.0, top_p: float = 0.9, **kwargs) -> Tensor:
         """src/models.py:748-771 (top_k before top_i, as there); **kwargs: ImageCaptioningModel.generate's extras."""
@@ -349,6 +396,15 @@ class RetrievalAugmentedTransformer(ImageCaptioningModel):
     def generate_captions(self, db_store, top_k: int, top_i: int, image_embeddings: Tensor, **kwargs) -> List[str]:
         ids = self.generate(db_store, top_k, top_i, image_embeddings, **kwargs)
         return self.tokenizer.batch_decode(ids, skip_special_tokens=True)
+
+
+def labels_from_mask(caption_token_ids: Tensor, attention_mask: Optional[Tensor] = None) -> Tensor:
+    """int64 labels of a caption batch: the ids where attention_mask == 1 (every id without a mask), -100 elsewhere
+    (the datasets' rule, icap/dataset.py)."""
+    ids = caption_token_ids.to(torch.int64)
+    if attention_mask is None:
+        return ids.clone()
+    return torch.where(attention_mask.to(ids.device) == 1, ids, torch.full_like(ids, -100))
 
 
 def _embedding_grads(d_emb: Tensor, ids: Tensor, B: int, P: int, Lc: int, D: int, g, dwh: DWHelper) -> None:

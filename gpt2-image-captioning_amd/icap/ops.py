@@ -682,6 +682,47 @@ def cross_entropy(logits: Tensor, V: int, labels: Tensor, n_valid: Tensor, loss:
     return loss
 
 
+def caption_score_workspace(rows: int) -> int:
+    return int(L.load().icap_caption_score_workspace_bytes(rows))
+
+
+def caption_target_ranges(B: int, S: int, ranges: Tensor, row_slot: Optional[Tensor] = None, seqs=None) -> Tensor:
+    """ranges int32 [B + 1] for caption_score (include/icap.h icap_caption_target_ranges): row_slot None — logits on
+    the padded [B, S] grid; row_slot — compacted target rows; seqs = (seq_off, seq_len) — packed grid rows."""
+    if ranges.dtype != torch.int32 or ranges.numel() < B + 1:
+        raise L.IcapError("caption_target_ranges: ranges must be int32 [B + 1]")
+    so, sl = (seqs[0].data_ptr(), seqs[1].data_ptr()) if seqs is not None else (None, None)
+    call("icap_caption_target_ranges", B, S, _p(row_slot), so, sl, ranges.data_ptr(), _stream())
+    return ranges
+
+
+def caption_score(logits: Tensor, V: int, labels: Tensor, ranges: Tensor, nll: Tensor, n_tokens: Tensor,
+                  n_correct: Tensor, workspace: Tensor, *, rows: Optional[int] = None,
+                  rows_dev: Optional[Tensor] = None, token_logprobs: Optional[Tensor] = None, P: int = 0, Lc: int = 0,
+                  row_slot: Optional[Tensor] = None, seqs=None, totals: Optional[Tensor] = None) -> Tensor:
+    """Per-caption nll / target count / correct count from LM-head logits (include/icap.h icap_caption_score).
+    labels int32 per row (negative: ignored); ranges int32 [B + 1]; totals float64 [3], added to."""
+    rows = logits.shape[0] if rows is None else rows
+    B = nll.shape[0]
+    if labels.dtype != torch.int32 or ranges.dtype != torch.int32 or ranges.numel() < B + 1:
+        raise L.IcapError("caption_score: labels and ranges must be int32 ([rows], [B + 1])")
+    if nll.dtype != torch.float32 or n_tokens.dtype != torch.int32 or n_correct.dtype != torch.int32:
+        raise L.IcapError("caption_score: nll must be float32, n_tokens / n_correct int32")
+    if n_tokens.numel() < B or n_correct.numel() < B:
+        raise L.IcapError("caption_score: n_tokens / n_correct must hold B elements")
+    if token_logprobs is not None and (token_logprobs.dtype != torch.float32 or token_logprobs.numel() < B * Lc):
+        raise L.IcapError("caption_score: token_logprobs must be float32 [B, Lc]")
+    if totals is not None and (totals.dtype != torch.float64 or totals.numel() < 3):
+        raise L.IcapError("caption_score: totals must be float64 [3]")
+    if workspace.numel() * workspace.element_size() < caption_score_workspace(rows):
+        raise L.IcapError("caption_score: workspace too small (caption_score_workspace(rows))")
+    so, sl = (seqs[0].data_ptr(), seqs[1].data_ptr()) if seqs is not None else (None, None)
+    call("icap_caption_score", dtype_code(logits.dtype), rows, V, logits.data_ptr(), _ld(logits), labels.data_ptr(),
+         _p(rows_dev), B, ranges.data_ptr(), nll.data_ptr(), n_tokens.data_ptr(), n_correct.data_ptr(),
+         _p(token_logprobs), P, Lc, _p(row_slot), so, sl, _p(totals), workspace.data_ptr(), _stream())
+    return nll
+
+
 def adamw_workspace(n: int) -> int:
     return int(L.load().icap_adamw_workspace_bytes(n))
 

@@ -34,11 +34,24 @@ def train(train_dataset, model, batch_size: int, num_epochs: int, num_workers: i
           outputs_dir: str = "checkpoints", grad_accum_steps: int = 1, val_dataset=None,
           val_annotations_path: Optional[str] = None, eval_every_epoch: int = 1, eval_batch_size: Optional[int] = None,
           eval_max_length: int = 50, eval_temperature: float = 0.0, eval_top_p: float = 0.9, *, clip_model=None,
-          use_graph: bool = True, log_every: int = 0, dropout: bool = True, seed: int = 0) -> dict[str, Any]:
+          use_graph: bool = True, log_every: int = 0, dropout: bool = True, seed: int = 0, eval_loss: bool = False,
+          select_by: str = "cider") -> dict[str, Any]:
+    """eval_loss: each validation epoch also scores every validation caption teacher-forced (evaluate.evaluate_loss)
+    and its dict gains val_loss / val_perplexity / val_token_accuracy; the return dict gains best_val_loss.
+    select_by: "cider" (the reference's rule) or "val_loss" (needs eval_loss): which metric decides the
+    best_model_epoch_{e}.pt checkpoint and best_epoch."""
+    _check_selection(eval_loss, select_by)
     return _fit(None, train_dataset, model, batch_size, num_epochs, num_workers, learning_rate, num_warmup_steps,
                 save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset, val_annotations_path,
                 eval_every_epoch, eval_batch_size, eval_max_length, eval_temperature, eval_top_p, clip_model,
-                use_graph, log_every, dropout, seed)
+                use_graph, log_every, dropout, seed, eval_loss, select_by)
+
+
+def _check_selection(eval_loss: bool, select_by: str) -> None:
+    if select_by not in ("cider", "val_loss"):
+        raise ValueError(f'select_by must be "cider" or "val_loss", not {select_by!r}')
+    if select_by == "val_loss" and not eval_loss:
+        raise ValueError('select_by="val_loss" needs eval_loss=True')
 
 
 def train_rat(train_dataset, model, db_store, top_k: int, top_i: int, batch_size: int, num_epochs: int,
@@ -47,12 +60,14 @@ def train_rat(train_dataset, model, db_store, top_k: int, top_i: int, batch_size
               val_dataset=None, val_annotations_path: Optional[str] = None, eval_every_epoch: int = 1,
               eval_batch_size: Optional[int] = None, eval_max_length: int = 50, eval_temperature: float = 0.0,
               eval_top_p: float = 0.9, *, clip_model=None, use_graph: bool = True, log_every: int = 0,
-              dropout: bool = True, seed: int = 0) -> dict[str, Any]:
+              dropout: bool = True, seed: int = 0, eval_loss: bool = False,
+              select_by: str = "cider") -> dict[str, Any]:
     """src/train.py:257-483 for a RetrievalAugmentedTransformer: train() with one added step per batch. The batch's
     image embeddings go to the device, model.augment (score GEMM, top-k, aggregate: no host synchronisation) replaces
     them by embedding + aggregated retrieval, and the fused step runs on the result. The best model is saved as
     best_rat_model_epoch_{e}.pt and validation goes through evaluate_rat_epoch. Under torch.distributed every rank
     holds a full replica of db_store on its own device."""
+    _check_selection(eval_loss, select_by)
     if clip_model is not None:
         raise ValueError("train_rat takes precomputed image embeddings: retrieval augments the embedding before the "
                          "step, so clip_model (pixels inside the step's graph) is not supported")
@@ -61,13 +76,13 @@ def train_rat(train_dataset, model, db_store, top_k: int, top_i: int, batch_size
     return _fit((db_store, top_k, top_i), train_dataset, model, batch_size, num_epochs, num_workers, learning_rate,
                 num_warmup_steps, save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset,
                 val_annotations_path, eval_every_epoch, eval_batch_size, eval_max_length, eval_temperature,
-                eval_top_p, None, use_graph, log_every, dropout, seed)
+                eval_top_p, None, use_graph, log_every, dropout, seed, eval_loss, select_by)
 
 
 def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learning_rate, num_warmup_steps,
          save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset, val_annotations_path, eval_every_epoch,
          eval_batch_size, eval_max_length, eval_temperature, eval_top_p, clip_model, use_graph, log_every, dropout,
-         seed) -> dict[str, Any]:
+         seed, eval_loss=False, select_by="cider") -> dict[str, Any]:
     """The loop of train() and train_rat(); rat = (db_store, top_k, top_i) or None."""
     os.makedirs(outputs_dir, exist_ok=True)
     eval_dir = os.path.join(outputs_dir, "eval_results")
@@ -104,6 +119,7 @@ def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learnin
     epoch_loss_values: list[float] = []
     val_metrics_history: list[dict[str, Any]] = []
     best_val_cider, best_epoch = -1.0, 0
+    best_val_loss = math.inf
     step_idx = 0
     n_batches = len(dl)
     for epoch in range(num_epochs):
@@ -160,14 +176,26 @@ def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learnin
                 m = evaluate_rat_epoch(model, rat[0], rat[1], rat[2], val_dataset, val_annotations_path, epoch + 1,
                                        "val", eval_batch_size, num_workers, eval_max_length, eval_temperature,
                                        eval_top_p, device, eval_dir)
+            if is_main and eval_loss:  # every validation caption teacher-forced, totals on the device
+                from .evaluate import LOSS_KEYS, evaluate_loss
+
+                vl = evaluate_loss(model, val_dataset, eval_batch_size, num_workers, device, rat=rat,
+                                   use_graph=use_graph)
+                m = {**m, **{k: vl[k] for k in LOSS_KEYS}}
             if dist:
                 box = [m]
                 torch.distributed.broadcast_object_list(box, src=0)
                 m = box[0]
             val_metrics_history.append({"epoch": epoch + 1, "loss": avg, **m})
             cider = m.get("CIDEr", -1.0)
-            if cider > best_val_cider:
-                best_val_cider, best_epoch = cider, epoch + 1
+            better_cider = cider > best_val_cider
+            if better_cider:
+                best_val_cider = cider
+            better_loss = eval_loss and m["val_loss"] < best_val_loss
+            if better_loss:
+                best_val_loss = m["val_loss"]
+            if better_loss if select_by == "val_loss" else better_cider:
+                best_epoch = epoch + 1
                 if is_main:
                     best = "best_model_epoch" if rat is None else "best_rat_model_epoch"  # src/train.py:445-447
                     model.save_parameters(os.path.join(outputs_dir, f"{best}_{best_epoch}.pt"))
@@ -176,5 +204,8 @@ def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learnin
         from .evaluate import save_eval_summary
 
         save_eval_summary(val_metrics_history, os.path.join(eval_dir, "val_metrics_summary.json"))
-    return {"epoch_losses": epoch_loss_values, "val_metrics": val_metrics_history, "best_val_cider": best_val_cider,
-            "best_epoch": best_epoch}
+    out = {"epoch_losses": epoch_loss_values, "val_metrics": val_metrics_history, "best_val_cider": best_val_cider,
+           "best_epoch": best_epoch}
+    if eval_loss:
+        out["best_val_loss"] = best_val_loss
+    return out

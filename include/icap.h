@@ -354,6 +354,49 @@ int icap_cross_entropy(int32_t dtype, int64_t rows, int64_t V, const void* logit
                        void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Teacher-forced caption scoring: the loss above (src/models.py:286-325,     */
+/* HF/loss/loss_utils.py:32-71) taken apart per caption, forward only.        */
+/* Row r of logits [rows, ld] (bf16 or fp32, V <= ld, ld % 4 == 0, columns    */
+/* V..ld never read) has label labels[r]; negative = ignored. Sequence b owns */
+/* rows ranges[b] .. ranges[b+1]-1 (int32 [B+1], icap_caption_target_ranges), */
+/* clipped to [0, min(rows, *rows_dev)). Over its rows with a label:          */
+/*   nll[b]       = sum (lse(x_r[:V]) - x_r[y_r]): the rows' fp32 values added */
+/*                  in row order in double, rounded once (0 without a target) */
+/*   n_tokens[b]  = number of such rows                                       */
+/*   n_correct[b] = those whose label is the FIRST maximum of the V logits    */
+/*                  (torch.argmax: ties to the lower index, NaN the maximum)  */
+/* A row holding a NaN scores NaN, a +inf logit gives lse = +inf; a label     */
+/* >= V is counted and scores NaN.                                            */
+/* workspace: fp32 [rows] per-row nll (0 on ignored rows), then int32 [rows]  */
+/* per-row hit. rows_dev (optional device int32): rows at or beyond *rows_dev */
+/* are neither read nor written.                                              */
+/* token_logprobs (optional fp32 [B, Lc], needs P and Lc): -(per-row nll) of  */
+/* the row that predicts caption token t (position P + t - 1 of sequence b),  */
+/* 0 where that token has no label. The row is found as                       */
+/*   grid row g = seq_off ? seq_off[b] + pos (pos < seq_len[b]) : b*(P+Lc)+pos */
+/*   logits row = row_slot ? row_slot[g] : g                                   */
+/* i.e. row_slot NULL for logits on the padded grid, row_slot for compacted   */
+/* target rows, seq_off / seq_len (both or neither; they need row_slot) when  */
+/* the grid rows are packed (icap_caption_pack).                              */
+/* totals (optional device double [3]): sum_b (double)nll[b], sum n_tokens,   */
+/* sum n_correct are ADDED to it in sequence order by one wave. No atomics    */
+/* anywhere: the results are bitwise reproducible.                            */
+/* ------------------------------------------------------------------------- */
+size_t icap_caption_score_workspace_bytes(int64_t rows);
+int icap_caption_score(int32_t dtype, int64_t rows, int64_t V, const void* logits, int64_t ld,
+                       const int32_t* labels, const int32_t* rows_dev, int32_t B, const int32_t* ranges,
+                       float* nll, int32_t* n_tokens, int32_t* n_correct, float* token_logprobs,
+                       int32_t P, int32_t Lc, const int32_t* row_slot, const int32_t* seq_off,
+                       const int32_t* seq_len, double* totals, void* workspace, void* stream);
+/* ranges [B+1] for icap_caption_score from what icap_caption_prep / icap_caption_pack wrote:         */
+/*   row_slot NULL (logits on the padded [B, S] grid): ranges[b] = b*S;                                */
+/*   row_slot [B*S] (compacted target rows, which keep row order): ranges[b] = number of target rows   */
+/*   before sequence b's grid rows, those being b*S .. (b+1)*S-1, or with seq_off / seq_len (packed    */
+/*   rows, both or neither) seq_off[b] .. seq_off[b]+seq_len[b]-1.                                     */
+int icap_caption_target_ranges(int32_t B, int32_t S, const int32_t* row_slot, const int32_t* seq_off,
+                               const int32_t* seq_len, int32_t* ranges, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Global grad-norm clip + AdamW + linear LR schedule over ONE flat fp32       */
 /* parameter buffer (src/train.py:94-103,150-159; TORCH/nn/utils/clip_grad.py */
 /* :121-186; TORCH/optim/adam.py:419,457,476,499,545-547;                       */
