@@ -499,6 +499,8 @@ extern "C" int icap_layernorm_bwd(int32_t dtype, int64_t rows, int64_t D, const 
                      (dx_drop == nullptr || ln8_ok(dtype, D, dx_drop, lddx));
   ICAP_REQUIRE(D > 0 && D % 4 == 0 && (D <= 4 * 64 * LN_MAXV || (D <= LN8_DMAX && wide8)),
                "icap_layernorm_bwd: D must be a multiple of 4, <= 1024 (<= 1536 with 16-byte rows)");
+  ICAP_REQUIRE(ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && (dres == nullptr || lddres % 4 == 0),
+               "icap_layernorm_bwd: strides must be multiples of 4");
   ICAP_REQUIRE((dgamma == nullptr && dbeta == nullptr) || workspace != nullptr,
                "icap_layernorm_bwd: dgamma/dbeta need a workspace");
   ICAP_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "icap_layernorm_bwd: drop_p out of range");

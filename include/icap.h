@@ -200,7 +200,10 @@ int icap_gemm_group(const icap_gemm_args* a, int32_t n, void* stream);
 /* modeling_gpt2.py:252-254,497,620; mapper norm1/norm2 TORCH transformer.py  */
 /* :946-950; CLIP pre/post/layer_norm1/2 modeling_clip.py:641-651,365-384).   */
 /* y = (x-mean)*rstd*gamma + beta; mean/rstd (fp32 [rows]) saved for backward. */
-/* D % 4 == 0, D <= 1024.                                                      */
+/* D % 4 == 0, D <= 1024 (<= 1536 with 16-byte aligned rows and strides that   */
+/* are multiples of 8). Every row stride of either entry point (ldx, ldy;      */
+/* ldx, lddy, lddx, and lddres when dres is given) must be a multiple of 4;    */
+/* dx_drop shares dx's stride lddx.                                            */
 /* ------------------------------------------------------------------------- */
 /* y_rowmap (optional int32 [rows]): row r is stored to y row y_rowmap[r], or  */
 /* not at all when it is < 0 (gathers the LM-head target rows).                */
