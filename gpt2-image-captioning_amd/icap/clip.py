@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import gpt2 as _gpt2
 from . import ops
-from .gpt2 import fold_layernorm
+from .encoder import ImageEncoderCore, cached_core
 from .weights import det_tensor
 
 Tensor = torch.Tensor
@@ -88,6 +88,13 @@ class _Encoder(nn.Module):
         self.layers = nn.ModuleList([_Layer(c) for _ in range(c.num_hidden_layers)])
 
 
+def encoder_layer_weights(core, lay: _Layer):
+    """One CLIP encoder layer (vision or text: the same modules) in `core`'s GEMM layout."""
+    a = lay.self_attn
+    return core.layer_weights(a.q_proj, a.k_proj, a.v_proj, a.out_proj, lay.mlp.fc1, lay.mlp.fc2,
+                              lay.layer_norm1, lay.layer_norm2)
+
+
 class _VisionModel(nn.Module):
     def __init__(self, c):
         super().__init__()
@@ -107,8 +114,6 @@ class CLIPVisionTower(nn.Module):
         self.visual_projection = nn.Linear(self.config.hidden_size, self.config.projection_dim, bias=False)
         for p in self.parameters():
             p.requires_grad = False  # frozen encoder (clip.py:30 eval mode, no training)
-        self._core = None
-        self._core_key = None
 
     @classmethod
     def random_init(cls, config: Optional[CLIPVisionConfig] = None, seed: int = 0) -> "CLIPVisionTower":
@@ -147,11 +152,7 @@ class CLIPVisionTower(nn.Module):
         return self.visual_projection.weight.device
 
     def core(self, dtype: torch.dtype = torch.bfloat16) -> "ClipCore":
-        key = (dtype, self.device)
-        if self._core is None or self._core_key != key:
-            self._core = ClipCore(self, dtype)
-            self._core_key = key
-        return self._core
+        return cached_core(self, ClipCore, dtype)
 
     @torch.no_grad()
     def get_image_features(self, pixel_values: Tensor, compute_dtype: torch.dtype = torch.bfloat16) -> Tensor:
@@ -164,151 +165,43 @@ class CLIPVisionTower(nn.Module):
         return self.core(compute_dtype).features(pixel_values, normalize=True)
 
 
-class ClipCore:
-    def __init__(self, m: CLIPVisionTower, dtype: torch.dtype):
-        from ._lib import require_device
+class ClipCore(ImageEncoderCore):
+    """Kernel schedule of one CLIPVisionTower in one compute dtype: [CLS || patches] + positions -> pre_layrnorm ->
+    the encoder layers (quick_gelu) -> post_layernorm(CLS) -> visual_projection -> L2 normalise."""
 
-        self.m, self.dtype = m, dtype
-        self.dev = m.device
-        require_device(self.dev)
-        c = m.config
-        self.c = c
-        self.D, self.H = c.hidden_size, c.num_attention_heads
-        self.hd = self.D // self.H
-        self.G = c.image_size // c.patch_size
-        self.S = self.G * self.G + 1
-        self.refresh()
-        self._ws = {}
-
-    def _cvt(self, t: Tensor) -> Tensor:
-        t2 = t.reshape(t.shape[0], -1)
-        if self.dtype == torch.float32:
-            return t2.contiguous()
-        out = torch.empty(t2.shape, dtype=self.dtype, device=self.dev)
-        ops.convert(t2.contiguous(), out)
-        return out
+    act = L.ACT_QUICK_GELU
+    raw = "feat32"
 
     @torch.no_grad()
     def refresh(self):
-        vm, dt = self.m.vision_model, self.dtype
-        # bf16: layer_norm1 (layers >= 1) / layer_norm2 (all but the last) folded into the QKV / fc1 tile GEMMs, the row
-        # statistics handed over from the producing GEMMs' epilogues (icap_gemm_args.ln_stats_out / ln_stats_in)
-        self.fold = dt == torch.bfloat16 and ops.ln_fold_ok(self.D) and _gpt2.TRAIN_LN_FOLD
-        # [D, C*p*p] (c, ky, kx) order, zero-padded to the 8-multiple row of icap_im2col_patches (p = 14: 592)
-        wp = vm.embeddings.patch_embedding.weight.data.reshape(self.D, -1)
-        self.Kp = (wp.shape[1] + 7) // 8 * 8
+        vm, emb = self.m.vision_model, self.m.vision_model.embeddings
+        self.fold = self.dtype == torch.bfloat16 and ops.ln_fold_ok(self.D) and _gpt2.TRAIN_LN_FOLD
         # bf16 towers: the fused gather GEMM (icap_patch_embed) where it is the faster form. Measured round 6
         # (profiles/r06_patch_bench.txt, B = 128): ViT-B/32 fused 101.0 us vs im2col + the split-role GEMM (96 x 128
         # tiles) + vit_embed 85.8 us — the fused kernel's 6 column tiles each re-gather their rows' fp32 pixels;
         # ViT-L/14 fused 200.5 vs 221.5 us (K = 588: the GEMM is short, the im2col pass is not)
-        self.fused_patch = self.dtype == torch.bfloat16 and self.c.patch_size != 32
-        if self.Kp != wp.shape[1]:
-            wp = torch.nn.functional.pad(wp, (0, self.Kp - wp.shape[1]))
-        self.w_patch = self._cvt(wp)
-        self.cls = vm.embeddings.class_embedding.data
-        self.pos = vm.embeddings.position_embedding.weight.data
+        self.patch_weights(emb.patch_embedding, emb.class_embedding.data, emb.position_embedding.weight.data,
+                           fused=self.dtype == torch.bfloat16 and self.c.patch_size != 32)
         self.pre = (vm.pre_layrnorm.weight.data, vm.pre_layrnorm.bias.data)
         self.post = (vm.post_layernorm.weight.data, vm.post_layernorm.bias.data)
         self.w_proj = self._cvt(self.m.visual_projection.weight.data)
-        self.layers = []
-        for lay in vm.encoder.layers:
-            a = lay.self_attn
-            w = SimpleNamespace()
-            w.qkv_w = self._cvt(torch.cat([a.q_proj.weight.data, a.k_proj.weight.data, a.v_proj.weight.data], 0))
-            w.qkv_b = torch.cat([a.q_proj.bias.data, a.k_proj.bias.data, a.v_proj.bias.data], 0).contiguous()
-            w.out_w, w.out_b = self._cvt(a.out_proj.weight.data), a.out_proj.bias.data
-            w.fc1_w, w.fc1_b = self._cvt(lay.mlp.fc1.weight.data), lay.mlp.fc1.bias.data
-            w.fc2_w, w.fc2_b = self._cvt(lay.mlp.fc2.weight.data), lay.mlp.fc2.bias.data
-            w.ln1 = (lay.layer_norm1.weight.data, lay.layer_norm1.bias.data)
-            w.ln2 = (lay.layer_norm2.weight.data, lay.layer_norm2.bias.data)
-            if self.fold:  # layer_norm1 / layer_norm2 folded into the QKV / fc1 weights (frozen tower: once)
-                qkv32 = torch.cat([a.q_proj.weight.data, a.k_proj.weight.data, a.v_proj.weight.data], 0)
-                w.qkv_wf, w.qkv_ws, w.qkv_bf = fold_layernorm(qkv32, w.ln1[0], w.ln1[1], w.qkv_b, dt)
-                w.fc1_wf, w.fc1_ws, w.fc1_bf = fold_layernorm(lay.mlp.fc1.weight.data, w.ln2[0], w.ln2[1], w.fc1_b, dt)
-            self.layers.append(w)
+        self.layers = [encoder_layer_weights(self, lay) for lay in vm.encoder.layers]
 
-    def alloc(self, B: int) -> SimpleNamespace:
-        if B in self._ws:
-            return self._ws[B]
-        c, D, dt, dev = self.c, self.D, self.dtype, self.dev
-        M = B * self.S
-        e = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-        ws = SimpleNamespace(B=B, M=M)
-        if not self.fused_patch:  # (icap_patch_embed reads the pixels itself — no patch matrix)
-            ws.patches = e(B * self.G * self.G, self.Kp)
-            ws.pe = e(B * self.G * self.G, D)
-        ws.x, ws.h1, ws.a, ws.o = e(M, D), e(M, D), e(M, D), e(M, D)
-        ws.qkv = e(M, 3 * D)
-        ws.f = e(M, c.intermediate_size)
-        ws.pooled = e(B, D)
-        ws.xc = e(B, D)  # the last layer's CLS rows (see run)
-        ws.feat = e(B, c.projection_dim)
-        ws.emb = e(B, c.projection_dim, dtype=torch.float32)
-        ws.feat32 = e(B, c.projection_dim, dtype=torch.float32)
-        ws.st_x = ws.st_h = None
-        if self.fold:  # (mean, M2) per row and 32-column group of x / h1 (the LayerNorm statistics hand-off)
-            ws.st_x = e(M, D // 32, 2, dtype=torch.float32)
-            ws.st_h = e(M, D // 32, 2, dtype=torch.float32)
-        self._ws = {B: ws}  # keep only the latest batch size
-        return ws
+    def alloc_head(self, ws):
+        e, p = self._empty, self.c.projection_dim
+        ws.pooled = e(ws.B, self.D)
+        ws.emb, ws.feat32 = e(ws.B, p, dtype=torch.float32), e(ws.B, p, dtype=torch.float32)
 
-    def run(self, ws, pixels: Tensor) -> Tensor:
-        """Kernel schedule; returns ws.emb (fp32, L2-normalised) — graph-capturable."""
-        c, D, B = self.c, self.D, ws.B
-        eps = c.layer_norm_eps
-        if self.fused_patch:
-            # Conv2d(stride=patch, bias=False) + [CLS || patches] + positions in one launch that gathers the pixel runs
-            # into its LDS stages (round 5: no im2col patch matrix, no separate embedding pass)
-            ops.patch_embed(pixels, self.w_patch, ws.h1, patch=c.patch_size, prefix=self.cls.view(1, D), pos=self.pos)
-        else:  # the im2col matrix (bf16 / fp32 parity mode) and the GEMM over it
-            ops.im2col_patches(pixels, ws.patches, c.patch_size)
-            ops.gemm(ws.patches, self.w_patch, ws.pe)  # Conv2d(stride=patch, bias=False) as a GEMM
-            ops.vit_embed(ws.pe, self.cls, self.pos, ws.h1, B, self.G * self.G, D)
-        ops.layernorm_fwd(ws.h1, self.pre[0], self.pre[1], eps, ws.x, None, None)
-        scale = self.hd ** -0.5
-        nl = len(self.layers)
-        fold = ws.st_x is not None
-        for i, w in enumerate(self.layers):
-            if fold and i > 0:  # x's statistics come from the previous layer's fc2 epilogue
-                ops.gemm(ws.x, w.qkv_wf, ws.qkv, bias=w.qkv_bf, ln_fold=(w.qkv_ws, eps), ln_stats_in=ws.st_x)
-            else:
-                ops.layernorm_fwd(ws.x, w.ln1[0], w.ln1[1], eps, ws.a, None, None)
-                ops.gemm(ws.a, w.qkv_w, ws.qkv, bias=w.qkv_b)
-            ops.attention_fwd(ws.qkv, ws.o, B=B, S=self.S, H=self.H, hd=self.hd, scale=scale, causal=False)
-            if i == nl - 1:
-                # last layer: only the CLS rows reach the output (pooler_output = post_layernorm(last_hidden[:, 0]),
-                # modeling_clip.py:741-752), so the rows past attention — out_proj, LayerNorm 2, the MLP — run on the
-                # B CLS rows alone (strided views: row b at b*S*D); every other token's keys / values were used above
-                o_c, x_c = ws.o.view(B, self.S * D)[:, :D], ws.x.view(B, self.S * D)[:, :D]
-                h1, a, f = ws.h1[:B], ws.a[:B], ws.f[:B]
-                ops.gemm(o_c, w.out_w, h1, bias=w.out_b, resid=x_c)
-                ops.layernorm_fwd(h1, w.ln2[0], w.ln2[1], eps, a, None, None)
-                ops.gemm(a, w.fc1_w, f, bias=w.fc1_b, act=L.ACT_QUICK_GELU)
-                ops.gemm(f, w.fc2_w, ws.xc, bias=w.fc2_b, resid=h1)
-                break
-            if fold:
-                ops.gemm(ws.o, w.out_w, ws.h1, bias=w.out_b, resid=ws.x, ln_stats_out=ws.st_h)
-                ops.gemm(ws.h1, w.fc1_wf, ws.f, bias=w.fc1_bf, act=L.ACT_QUICK_GELU, ln_fold=(w.fc1_ws, eps),
-                         ln_stats_in=ws.st_h)
-                ops.gemm(ws.f, w.fc2_w, ws.x, bias=w.fc2_b, resid=ws.h1, ln_stats_out=ws.st_x)
-                continue
-            ops.gemm(ws.o, w.out_w, ws.h1, bias=w.out_b, resid=ws.x)
-            ops.layernorm_fwd(ws.h1, w.ln2[0], w.ln2[1], eps, ws.a, None, None)
-            ops.gemm(ws.a, w.fc1_w, ws.f, bias=w.fc1_b, act=L.ACT_QUICK_GELU)
-            ops.gemm(ws.f, w.fc2_w, ws.x, bias=w.fc2_b, resid=ws.h1)
-        cls_rows = ws.xc  # CLS token of every image after the last layer
-        ops.layernorm_fwd(cls_rows, self.post[0], self.post[1], eps, ws.pooled, None, None, rows=B)
+    def embed(self, ws, pixels: Tensor):
+        self.embed_patches(ws, pixels, ws.h1)
+        ops.layernorm_fwd(ws.h1, self.pre[0], self.pre[1], self.c.layer_norm_eps, ws.x, None, None)
+
+    def head(self, ws):
+        # only the CLS rows reach the output (pooler_output = post_layernorm(last_hidden[:, 0]), modeling_clip.py:
+        # 741-752), which is why the last layer ran past its attention on those rows alone (encode): they are in ws.xc
+        ops.layernorm_fwd(ws.xc, self.post[0], self.post[1], self.c.layer_norm_eps, ws.pooled, None, None, rows=ws.B)
         ops.gemm(ws.pooled, self.w_proj, ws.feat32)
         ops.l2norm_rows(ws.feat32, ws.emb)
-        return ws.emb
-
-    @torch.no_grad()
-    def features(self, pixels: Tensor, normalize: bool = True) -> Tensor:
-        if pixels.dtype != torch.float32 or not pixels.is_contiguous():
-            pixels = pixels.float().contiguous()
-        ws = self.alloc(pixels.shape[0])
-        self.run(ws, pixels)
-        return (ws.emb if normalize else ws.feat32).clone()
 
 
 # --------------------------------------------------------------------------- reference-shaped API (clip.py:10-149)

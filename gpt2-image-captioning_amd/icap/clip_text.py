@@ -29,7 +29,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .clip import _Encoder
+from .clip import _Encoder, encoder_layer_weights
+from .encoder import EncoderCore, cached_core
 from .weights import det_tensor
 
 Tensor = torch.Tensor
@@ -106,8 +107,6 @@ class CLIPTextTower(nn.Module):
         self.text_projection = nn.Linear(self.config.hidden_size, self.config.projection_dim, bias=False)
         for p in self.parameters():
             p.requires_grad = False  # frozen encoder
-        self._core = None
-        self._core_key = None
 
     @classmethod
     def random_init(cls, config: Optional[CLIPTextConfig] = None, seed: int = 0) -> "CLIPTextTower":
@@ -161,11 +160,7 @@ class CLIPTextTower(nn.Module):
         if self.device.type != "cuda":
             raise L.IcapError("CLIPTextTower: a host path of the CLIP text tower is not part of this build; move "
                               "the tower to the device (there is no host fallback)")
-        key = (dtype, self.device)
-        if getattr(self, "_core", None) is None or self._core_key != key:
-            self._core = ClipTextCore(self, dtype)
-            self._core_key = key
-        return self._core
+        return cached_core(self, ClipTextCore, dtype)
 
     @torch.no_grad()
     def get_text_features(self, input_ids: Tensor, attention_mask: Optional[Tensor] = None,
@@ -186,29 +181,14 @@ class CLIPTextTower(nn.Module):
         return self.core(compute_dtype).features(input_ids, normalize=True)
 
 
-class ClipTextCore:
-    """refresh / alloc / run, shaped like ClipCore. Workspaces are allocated once, for ROWS_CAP token rows and
-    CAPTIONS_CAP captions; `alloc(B, L)` hands out views of them, so a chunk of any shape under the caps runs (and
-    is captured into a HIP graph) without an allocation."""
+class ClipTextCore(EncoderCore):
+    """refresh / alloc / run over the shared encoder schedule (icap.encoder), causal. Workspaces are allocated once,
+    for ROWS_CAP token rows and CAPTIONS_CAP captions; `alloc(B, L)` hands out views of them, so a chunk of any shape
+    under the caps runs (and is captured into a HIP graph) without an allocation."""
 
-    def __init__(self, m: CLIPTextTower, dtype: torch.dtype):
-        self.m, self.dtype = m, dtype
-        self.dev = m.device
-        L.require_device(self.dev)
-        c = m.config
-        self.c = c
-        self.D, self.H = c.hidden_size, c.num_attention_heads
-        self.hd = self.D // self.H
-        self.refresh()
-        self._buf = None
-        self._ws = {}
-
-    def _cvt(self, t: Tensor) -> Tensor:
-        if self.dtype == torch.float32:
-            return t.contiguous()
-        out = torch.empty(t.shape, dtype=self.dtype, device=self.dev)
-        ops.convert(t.contiguous(), out)
-        return out
+    act = L.ACT_QUICK_GELU
+    causal = True
+    _buf = None
 
     @torch.no_grad()
     def refresh(self):
@@ -219,36 +199,19 @@ class ClipTextCore:
         self.pos = tm.embeddings.position_embedding.weight.data.contiguous()
         self.final = (tm.final_layer_norm.weight.data, tm.final_layer_norm.bias.data)
         self.w_proj = self._cvt(self.m.text_projection.weight.data)
-        self.layers = []
-        for lay in tm.encoder.layers:
-            a = lay.self_attn
-            w = SimpleNamespace()
-            w.qkv_w = self._cvt(torch.cat([a.q_proj.weight.data, a.k_proj.weight.data, a.v_proj.weight.data], 0))
-            w.qkv_b = torch.cat([a.q_proj.bias.data, a.k_proj.bias.data, a.v_proj.bias.data], 0).contiguous()
-            w.out_w, w.out_b = self._cvt(a.out_proj.weight.data), a.out_proj.bias.data
-            w.fc1_w, w.fc1_b = self._cvt(lay.mlp.fc1.weight.data), lay.mlp.fc1.bias.data
-            w.fc2_w, w.fc2_b = self._cvt(lay.mlp.fc2.weight.data), lay.mlp.fc2.bias.data
-            w.ln1 = (lay.layer_norm1.weight.data, lay.layer_norm1.bias.data)
-            w.ln2 = (lay.layer_norm2.weight.data, lay.layer_norm2.bias.data)
-            self.layers.append(w)
+        self.layers = [encoder_layer_weights(self, lay) for lay in tm.encoder.layers]
 
     def _buffers(self) -> SimpleNamespace:
         if self._buf is None:
-            c, D, dt, dev = self.c, self.D, self.dtype, self.dev
-            e = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-            R, Bc = ROWS_CAP, CAPTIONS_CAP
-            b = SimpleNamespace()
-            b.ids = e(R, dtype=torch.int64)
-            b.x, b.h1, b.a, b.o = e(R, D), e(R, D), e(R, D), e(R, D)
-            b.qkv = e(R, 3 * D)
-            b.f = e(R, c.intermediate_size)
+            e, D, Bc, p = self._empty, self.D, CAPTIONS_CAP, self.c.projection_dim
+            b = self.layer_buffers(ROWS_CAP, Bc)
+            b.ids = e(ROWS_CAP, dtype=torch.int64)
             # the last layer's pooled rows (one per caption)
-            b.op, b.xp, b.hp, b.ap, b.xc, b.pooled = (e(Bc, D) for _ in range(6))
-            b.fp = e(Bc, c.intermediate_size)
-            b.feat32 = e(Bc, c.projection_dim, dtype=torch.float32)
-            b.emb = e(Bc, c.projection_dim, dtype=torch.float32)
+            b.op, b.xp, b.hp, b.ap, b.pooled = (e(Bc, D) for _ in range(5))
+            b.fp = e(Bc, self.c.intermediate_size)
+            b.feat32, b.emb = e(Bc, p, dtype=torch.float32), e(Bc, p, dtype=torch.float32)
             b.pooled_row = e(Bc, dtype=torch.int32)
-            b.oov = torch.zeros(1, dtype=torch.int32, device=dev)
+            b.oov = torch.zeros(1, dtype=torch.int32, device=self.dev)
             self._buf = b
         return self._buf
 
@@ -263,7 +226,8 @@ class ClipTextCore:
         if ws is not None:
             return ws
         b, M = self._buffers(), B * L_
-        ws = SimpleNamespace(B=B, L=L_, M=M, ids=b.ids[:M].view(B, L_), oov=b.oov, pooled_row=b.pooled_row[:B])
+        ws = SimpleNamespace(B=B, L=L_, M=M, ids=b.ids[:M].view(B, L_), oov=b.oov, pooled_row=b.pooled_row[:B],
+                             st_x=None, st_h=None)
         for nm in ("x", "h1", "a", "o", "qkv", "f"):
             setattr(ws, nm, getattr(b, nm)[:M])
         for nm in ("op", "xp", "hp", "ap", "xc", "pooled", "fp", "feat32", "emb"):
@@ -279,35 +243,21 @@ class ClipTextCore:
         no host sync, no allocation. It neither zeroes nor reads ws.oov: under a captured graph ids outside the
         vocabulary are made harmless by the kernel (zero token term) and counted, and it is the caller who looks at
         the count."""
-        c, D, B, L_, M = self.c, self.D, ws.B, ws.L, ws.M
-        if ids.shape != (B, L_) or ids.dtype != torch.int64 or not ids.is_cuda or not ids.is_contiguous():
+        c = self.c
+        if ids.shape != (ws.B, ws.L) or ids.dtype != torch.int64 or not ids.is_cuda or not ids.is_contiguous():
             raise L.IcapError("ClipTextCore.run: ids must be a contiguous device int64 tensor [ws.B, ws.L]")
-        eps = c.layer_norm_eps
         ops.clip_text_embed(ids, self.tok, self.pos, c.eos_token_id, ws.x, ws.pooled_row, ws.oov)
-        scale = self.hd ** -0.5
-        nl = len(self.layers)
-        for i, w in enumerate(self.layers):
-            ops.layernorm_fwd(ws.x, w.ln1[0], w.ln1[1], eps, ws.a, None, None)
-            ops.gemm(ws.a, w.qkv_w, ws.qkv, bias=w.qkv_b)
-            ops.attention_fwd(ws.qkv, ws.o, B=B, S=L_, H=self.H, hd=self.hd, scale=scale, causal=True)
-            if i == nl - 1:
-                # last layer: only the pooled row of each caption reaches the output (modeling_clip.py:559-582), and
-                # every other row's keys / values were used above, so out_proj, LayerNorm 2 and the MLP run on those B
-                # rows alone — gathered, because which row it is depends on the ids
-                ops.rows_gather(ws.pooled_row, ws.o, ws.op, ws.x, ws.xp, n_src=M)
-                ops.gemm(ws.op, w.out_w, ws.hp, bias=w.out_b, resid=ws.xp)
-                ops.layernorm_fwd(ws.hp, w.ln2[0], w.ln2[1], eps, ws.ap, None, None)
-                ops.gemm(ws.ap, w.fc1_w, ws.fp, bias=w.fc1_b, act=L.ACT_QUICK_GELU)
-                ops.gemm(ws.fp, w.fc2_w, ws.xc, bias=w.fc2_b, resid=ws.hp)
-                break
-            ops.gemm(ws.o, w.out_w, ws.h1, bias=w.out_b, resid=ws.x)
-            ops.layernorm_fwd(ws.h1, w.ln2[0], w.ln2[1], eps, ws.a, None, None)
-            ops.gemm(ws.a, w.fc1_w, ws.f, bias=w.fc1_b, act=L.ACT_QUICK_GELU)
-            ops.gemm(ws.f, w.fc2_w, ws.x, bias=w.fc2_b, resid=ws.h1)
-        ops.layernorm_fwd(ws.xc, self.final[0], self.final[1], eps, ws.pooled, None, None)
+        self.encode(ws, ws.L)
+        ops.layernorm_fwd(ws.xc, self.final[0], self.final[1], c.layer_norm_eps, ws.pooled, None, None)
         ops.gemm(ws.pooled, self.w_proj, ws.feat32)
         ops.l2norm_rows(ws.feat32, ws.emb)
         return ws.emb
+
+    def pooled_rows(self, ws, S: int):
+        # only the pooled row of each caption reaches the output (modeling_clip.py:559-582) — gathered, not a strided
+        # view, because which row it is depends on the ids
+        ops.rows_gather(ws.pooled_row, ws.o, ws.op, ws.x, ws.xp, n_src=ws.M)
+        return ws.op, ws.xp, ws.hp, ws.ap, ws.fp
 
     @torch.no_grad()
     def features(self, input_ids: Tensor, normalize: bool = True) -> Tensor:

@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .encoder import ImageEncoderCore, cached_core
 from .weights import det_tensor
 
 Tensor = torch.Tensor
@@ -132,8 +133,6 @@ class DINOv3ImageTower(nn.Module):
         self.norm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
         for p in self.parameters():
             p.requires_grad = False
-        self._core = None
-        self._core_key = None
 
     @classmethod
     def random_init(cls, config: Optional[DinoConfig] = None, seed: int = 0) -> "DINOv3ImageTower":
@@ -189,11 +188,7 @@ class DINOv3ImageTower(nn.Module):
         return self.norm.weight.device
 
     def core(self, dtype: torch.dtype = torch.bfloat16) -> "DinoCore":
-        key = (dtype, self.device)
-        if self._core is None or self._core_key != key:
-            self._core = DinoCore(self, dtype)
-            self._core_key = key
-        return self._core
+        return cached_core(self, DinoCore, dtype)
 
     @torch.no_grad()
     def pooler_output(self, pixel_values: Tensor, compute_dtype: torch.dtype = torch.bfloat16) -> Tensor:
@@ -265,132 +260,44 @@ def meta_to_hf_state_dict(sd: Dict[str, Tensor], c: Optional[DinoConfig] = None)
     return out
 
 
-class DinoCore:
+class DinoCore(ImageEncoderCore):
     """Kernel schedule of one DINOv3ImageTower in one compute dtype (GEMM-layout weights, per-batch workspaces)."""
 
-    def __init__(self, m: DINOv3ImageTower, dtype: torch.dtype):
-        from ._lib import require_device
-
-        self.m, self.dtype = m, dtype
-        self.dev = m.device
-        require_device(self.dev)
-        c = m.config
-        self.c = c
-        self.D, self.H = c.hidden_size, c.num_attention_heads
-        self.hd = self.D // self.H
-        self.G = c.image_size // c.patch_size
-        self.NP = 1 + c.num_register_tokens
-        self.S = self.G * self.G + self.NP
-        self._ws = {}
-        self.refresh()
-
-    def _cvt(self, t: Tensor) -> Tensor:
-        t2 = t.reshape(t.shape[0], -1)
-        if self.dtype == torch.float32:
-            return t2.contiguous()
-        out = torch.empty(t2.shape, dtype=self.dtype, device=self.dev)
-        ops.convert(t2.contiguous(), out)
-        return out
+    act = L.ACT_GELU_ERF
 
     @torch.no_grad()
     def refresh(self):
-        m, D = self.m, self.D
+        m = self.m
         e = m.embeddings
-        wp = e.patch_embeddings.weight.data.reshape(D, -1)  # [D, C*p*p] in (c, ky, kx) order = im2col's
-        self.Kp = (wp.shape[1] + 7) // 8 * 8
-        if self.Kp != wp.shape[1]:
-            wp = torch.nn.functional.pad(wp, (0, self.Kp - wp.shape[1]))
-        self.w_patch = self._cvt(wp)
-        self.b_patch = e.patch_embeddings.bias.data.contiguous()
-        self.prefix = torch.cat([e.cls_token.data.reshape(1, D), e.register_tokens.data.reshape(-1, D)], 0).contiguous()
+        # [CLS || registers] in front of the patches, no absolute positions
+        self.patch_weights(e.patch_embeddings, torch.cat([e.cls_token.data, e.register_tokens.data], 1))
         self.lnf = (m.norm.weight.data, m.norm.bias.data)
         cos, sin = rope_tables(self.c, self.G, self.G)
         self.cos, self.sin = cos.to(self.dev), sin.to(self.dev)
         self.layers = []
-        for lay in m.model.layer:
+        for lay in m.model.layer:  # (k_proj has no bias; LayerScale folded into o_proj / down_proj)
             a = lay.attention
-            w = SimpleNamespace()
-            w.qkv_w = self._cvt(torch.cat([a.q_proj.weight.data, a.k_proj.weight.data, a.v_proj.weight.data], 0))
-            w.qkv_b = torch.cat([a.q_proj.bias.data, torch.zeros_like(a.q_proj.bias.data), a.v_proj.bias.data],
-                                0).contiguous()
-            l1, l2 = lay.layer_scale1.lambda1.data, lay.layer_scale2.lambda1.data
-            w.o_w = self._cvt(a.o_proj.weight.data * l1[:, None])  # LayerScale folded into the output rows
-            w.o_b = (a.o_proj.bias.data * l1).contiguous()
-            w.up_w, w.up_b = self._cvt(lay.mlp.up_proj.weight.data), lay.mlp.up_proj.bias.data.contiguous()
-            w.down_w = self._cvt(lay.mlp.down_proj.weight.data * l2[:, None])
-            w.down_b = (lay.mlp.down_proj.bias.data * l2).contiguous()
-            w.ln1 = (lay.norm1.weight.data, lay.norm1.bias.data)
-            w.ln2 = (lay.norm2.weight.data, lay.norm2.bias.data)
-            self.layers.append(w)
+            self.layers.append(self.layer_weights(a.q_proj, a.k_proj, a.v_proj, a.o_proj, lay.mlp.up_proj,
+                                                  lay.mlp.down_proj, lay.norm1, lay.norm2,
+                                                  out_scale=lay.layer_scale1.lambda1.data,
+                                                  fc2_scale=lay.layer_scale2.lambda1.data))
 
-    def alloc(self, B: int) -> SimpleNamespace:
-        if B in self._ws:
-            return self._ws[B]
-        c, D, dt, dev = self.c, self.D, self.dtype, self.dev
-        M = B * self.S
-        e = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-        ws = SimpleNamespace(B=B, M=M)
-        if dt != torch.bfloat16:  # (bf16: icap_patch_embed reads the pixels itself — no patch matrix)
-            ws.patches = e(B * self.G * self.G, self.Kp)
-            ws.pe = e(B * self.G * self.G, D)
-        ws.x, ws.h1, ws.a, ws.o = e(M, D), e(M, D), e(M, D), e(M, D)
-        ws.qkv = e(M, 3 * D)
-        ws.f = e(M, c.intermediate_size)
-        ws.cls = e(B, D)
-        ws.xc = e(B, D)  # the last layer's CLS rows (see run)
-        ws.pool = e(B, D, dtype=torch.float32)
-        ws.emb = e(B, D, dtype=torch.float32)
-        self._ws = {B: ws}  # keep only the latest batch size
-        return ws
+    def embed(self, ws, pixels: Tensor):
+        self.embed_patches(ws, pixels, ws.x)  # patch Conv2d (bias) + [CLS || registers || patches]
 
-    def run(self, ws, pixels: Tensor) -> Tensor:
-        """Kernel schedule; fills ws.pool (pooler_output, fp32) and ws.emb (L2-normalised) — graph-capturable."""
-        c, D, B, S = self.c, self.D, ws.B, self.S
-        eps = c.layer_norm_eps
-        if self.dtype == torch.bfloat16:  # patch Conv2d + [CLS || registers || patches], pixels read by the GEMM
-            ops.patch_embed(pixels, self.w_patch, ws.x, patch=c.patch_size, prefix=self.prefix, bias=self.b_patch)
-        else:
-            ops.im2col_patches(pixels, ws.patches, c.patch_size)
-            ops.gemm(ws.patches, self.w_patch, ws.pe, bias=self.b_patch)  # Conv2d(stride=patch, bias) as a GEMM
-            ops.prefix_embed(ws.pe, self.prefix, ws.x, B, self.G * self.G, D)  # [CLS || registers || patches]
-        scale = self.hd ** -0.5
-        nl = len(self.layers)
-        for i, w in enumerate(self.layers):
-            ops.layernorm_fwd(ws.x, w.ln1[0], w.ln1[1], eps, ws.a, None, None)
-            ops.gemm(ws.a, w.qkv_w, ws.qkv, bias=w.qkv_b)
-            ops.rope_patches(ws.qkv, self.cos, self.sin, B=B, S=S, NP=self.NP, H=self.H, hd=self.hd)
-            ops.attention_fwd(ws.qkv, ws.o, B=B, S=S, H=self.H, hd=self.hd, scale=scale, causal=False)
-            if i == nl - 1:
-                # last layer: pooler_output is the normed CLS row (modeling_dinov3_vit.py:540-541), so past attention
-                # the layer runs on the B CLS rows (strided views, row b at b*S*D); the registers' and patches' keys /
-                # values were used above
-                o_c, x_c = ws.o.view(B, S * D)[:, :D], ws.x.view(B, S * D)[:, :D]
-                h1, a, f = ws.h1[:B], ws.a[:B], ws.f[:B]
-                ops.gemm(o_c, w.o_w, h1, bias=w.o_b, resid=x_c)
-                ops.layernorm_fwd(h1, w.ln2[0], w.ln2[1], eps, a, None, None)
-                ops.gemm(a, w.up_w, f, bias=w.up_b, act=L.ACT_GELU_ERF)
-                ops.gemm(f, w.down_w, ws.xc, bias=w.down_b, resid=h1)
-                break
-            ops.gemm(ws.o, w.o_w, ws.h1, bias=w.o_b, resid=ws.x)
-            ops.layernorm_fwd(ws.h1, w.ln2[0], w.ln2[1], eps, ws.a, None, None)
-            ops.gemm(ws.a, w.up_w, ws.f, bias=w.up_b, act=L.ACT_GELU_ERF)
-            ops.gemm(ws.f, w.down_w, ws.x, bias=w.down_b, resid=ws.h1)
-        cls_rows = ws.xc  # CLS token of every image after the last layer
-        ops.layernorm_fwd(cls_rows, self.lnf[0], self.lnf[1], eps, ws.cls, None, None, rows=B)
+    def pre_attention(self, ws, S: int):
+        ops.rope_patches(ws.qkv, self.cos, self.sin, B=ws.B, S=S, NP=self.NP, H=self.H, hd=self.hd)
+
+    def head(self, ws):
+        # pooler_output is the normed CLS row (modeling_dinov3_vit.py:540-541), which is why the last layer ran past its
+        # attention on the CLS rows alone (encode: the registers' and patches' keys / values were used by then) and left
+        # them in ws.xc; fills ws.pool (pooler_output, fp32) and ws.emb
+        ops.layernorm_fwd(ws.xc, self.lnf[0], self.lnf[1], self.c.layer_norm_eps, ws.cls, None, None, rows=ws.B)
         if ws.cls.dtype == torch.float32:
             ws.pool.copy_(ws.cls)
         else:
             ops.convert(ws.cls, ws.pool)
         ops.l2norm_rows(ws.pool, ws.emb)
-        return ws.emb
-
-    @torch.no_grad()
-    def features(self, pixels: Tensor, normalize: bool = True) -> Tensor:
-        if pixels.dtype != torch.float32 or not pixels.is_contiguous():
-            pixels = pixels.float().contiguous()
-        ws = self.alloc(pixels.shape[0])
-        self.run(ws, pixels)
-        return (ws.emb if normalize else ws.pool).clone()
 
 
 # --------------------------------------------------------------------------- reference-shaped API (dino.py:19-185)

@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .encoder import ImageEncoderCore, cached_core
 from .weights import det_tensor
 
 Tensor = torch.Tensor
@@ -108,8 +109,6 @@ class ViTImageTower(nn.Module):
         self.pooler = _Dense(c.hidden_size, c.hidden_size)
         for p in self.parameters():
             p.requires_grad = False  # vit.py:31 eval mode, never trained
-        self._core = None
-        self._core_key = None
 
     @classmethod
     def random_init(cls, config: Optional[ViTConfig] = None, seed: int = 0) -> "ViTImageTower":
@@ -172,11 +171,7 @@ class ViTImageTower(nn.Module):
         return self.pooler.dense.weight.device
 
     def core(self, dtype: torch.dtype = torch.bfloat16) -> "ViTCore":
-        key = (dtype, self.device)
-        if self._core is None or self._core_key != key:
-            self._core = ViTCore(self, dtype)
-            self._core_key = key
-        return self._core
+        return cached_core(self, ViTCore, dtype)
 
     @torch.no_grad()
     def pooler_output(self, pixel_values: Tensor, compute_dtype: torch.dtype = torch.bfloat16) -> Tensor:
@@ -189,123 +184,35 @@ class ViTImageTower(nn.Module):
         return self.core(compute_dtype).features(pixel_values, normalize=True)
 
 
-class ViTCore:
+class ViTCore(ImageEncoderCore):
     """Kernel schedule of one ViTImageTower in one compute dtype (weights in GEMM layout, per-batch workspaces)."""
 
-    def __init__(self, m: ViTImageTower, dtype: torch.dtype):
-        from ._lib import require_device
-
-        self.m, self.dtype = m, dtype
-        self.dev = m.device
-        require_device(self.dev)
-        c = m.config
-        self.c = c
-        self.D, self.H = c.hidden_size, c.num_attention_heads
-        self.hd = self.D // self.H
-        self.G = c.image_size // c.patch_size
-        self.S = self.G * self.G + 1
-        self._ws = {}
-        self.refresh()
-
-    def _cvt(self, t: Tensor) -> Tensor:
-        t2 = t.reshape(t.shape[0], -1)
-        if self.dtype == torch.float32:
-            return t2.contiguous()
-        out = torch.empty(t2.shape, dtype=self.dtype, device=self.dev)
-        ops.convert(t2.contiguous(), out)
-        return out
+    act = L.ACT_GELU_ERF
 
     @torch.no_grad()
     def refresh(self):
         m = self.m
         e = m.embeddings
-        wp = e.patch_embeddings.projection.weight.data.reshape(self.D, -1)  # [D, C*p*p] in (c, ky, kx) order
-        self.Kp = (wp.shape[1] + 7) // 8 * 8  # icap_im2col_patches row width (p = 16: 768, no padding)
-        if self.Kp != wp.shape[1]:
-            wp = torch.nn.functional.pad(wp, (0, self.Kp - wp.shape[1]))
-        self.w_patch = self._cvt(wp)
-        self.b_patch = e.patch_embeddings.projection.bias.data.contiguous()
-        self.cls = e.cls_token.data.reshape(-1).contiguous()
-        self.pos = e.position_embeddings.data.reshape(self.S, self.D).contiguous()
+        self.patch_weights(e.patch_embeddings.projection, e.cls_token.data,
+                           e.position_embeddings.data.reshape(self.S, self.D).contiguous())
         self.lnf = (m.layernorm.weight.data, m.layernorm.bias.data)
         self.w_pool, self.b_pool = self._cvt(m.pooler.dense.weight.data), m.pooler.dense.bias.data
         self.layers = []
         for lay in m.encoder.layer:
             a = lay.attention.attention
-            w = SimpleNamespace()
-            w.qkv_w = self._cvt(torch.cat([a.query.weight.data, a.key.weight.data, a.value.weight.data], 0))
-            w.qkv_b = torch.cat([a.query.bias.data, a.key.bias.data, a.value.bias.data], 0).contiguous()
-            w.out_w, w.out_b = self._cvt(lay.attention.output.dense.weight.data), lay.attention.output.dense.bias.data
-            w.fc1_w, w.fc1_b = self._cvt(lay.intermediate.dense.weight.data), lay.intermediate.dense.bias.data
-            w.fc2_w, w.fc2_b = self._cvt(lay.output.dense.weight.data), lay.output.dense.bias.data
-            w.ln1 = (lay.layernorm_before.weight.data, lay.layernorm_before.bias.data)
-            w.ln2 = (lay.layernorm_after.weight.data, lay.layernorm_after.bias.data)
-            self.layers.append(w)
+            self.layers.append(self.layer_weights(a.query, a.key, a.value, lay.attention.output.dense,
+                                                  lay.intermediate.dense, lay.output.dense, lay.layernorm_before,
+                                                  lay.layernorm_after))
 
-    def alloc(self, B: int) -> SimpleNamespace:
-        if B in self._ws:
-            return self._ws[B]
-        c, D, dt, dev = self.c, self.D, self.dtype, self.dev
-        M = B * self.S
-        e = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-        ws = SimpleNamespace(B=B, M=M)
-        if dt != torch.bfloat16:  # (bf16: icap_patch_embed reads the pixels itself — no patch matrix)
-            ws.patches = e(B * self.G * self.G, self.Kp)
-            ws.pe = e(B * self.G * self.G, D)
-        ws.x, ws.h1, ws.a, ws.o = e(M, D), e(M, D), e(M, D), e(M, D)
-        ws.qkv = e(M, 3 * D)
-        ws.f = e(M, c.intermediate_size)
-        ws.cls = e(B, D)
-        ws.xc = e(B, D)  # the last layer's CLS rows (see run)
-        ws.pool = e(B, D, dtype=torch.float32)
-        ws.emb = e(B, D, dtype=torch.float32)
-        self._ws = {B: ws}  # keep only the latest batch size
-        return ws
+    def embed(self, ws, pixels: Tensor):
+        self.embed_patches(ws, pixels, ws.x)  # patch Conv2d (bias) + [CLS || patches] + positions; no pre-LN
 
-    def run(self, ws, pixels: Tensor) -> Tensor:
-        """Kernel schedule; fills ws.pool (pooler_output) and ws.emb (L2-normalised) — graph-capturable."""
-        c, D, B = self.c, self.D, ws.B
-        eps = c.layer_norm_eps
-        if self.dtype == torch.bfloat16:  # patch Conv2d + [CLS || patches] + positions, pixels read by the GEMM
-            ops.patch_embed(pixels, self.w_patch, ws.x, patch=c.patch_size, prefix=self.cls.view(1, D), pos=self.pos,
-                            bias=self.b_patch)
-        else:
-            ops.im2col_patches(pixels, ws.patches, c.patch_size)
-            ops.gemm(ws.patches, self.w_patch, ws.pe, bias=self.b_patch)  # Conv2d(stride=patch, bias) as a GEMM
-            ops.vit_embed(ws.pe, self.cls, self.pos, ws.x, B, self.G * self.G, D)  # [CLS || patches] + positions
-        scale = self.hd ** -0.5
-        nl = len(self.layers)
-        for i, w in enumerate(self.layers):
-            ops.layernorm_fwd(ws.x, w.ln1[0], w.ln1[1], eps, ws.a, None, None)
-            ops.gemm(ws.a, w.qkv_w, ws.qkv, bias=w.qkv_b)
-            ops.attention_fwd(ws.qkv, ws.o, B=B, S=self.S, H=self.H, hd=self.hd, scale=scale, causal=False)
-            if i == nl - 1:
-                # last layer: the pooler reads token 0 only (modeling_vit.py:289-301), so past attention the layer
-                # runs on the B CLS rows (strided views, row b at b*S*D); the other tokens' keys / values were used
-                o_c, x_c = ws.o.view(B, self.S * D)[:, :D], ws.x.view(B, self.S * D)[:, :D]
-                h1, a, f = ws.h1[:B], ws.a[:B], ws.f[:B]
-                ops.gemm(o_c, w.out_w, h1, bias=w.out_b, resid=x_c)
-                ops.layernorm_fwd(h1, w.ln2[0], w.ln2[1], eps, a, None, None)
-                ops.gemm(a, w.fc1_w, f, bias=w.fc1_b, act=L.ACT_GELU_ERF)
-                ops.gemm(f, w.fc2_w, ws.xc, bias=w.fc2_b, resid=h1)
-                break
-            ops.gemm(ws.o, w.out_w, ws.h1, bias=w.out_b, resid=ws.x)
-            ops.layernorm_fwd(ws.h1, w.ln2[0], w.ln2[1], eps, ws.a, None, None)
-            ops.gemm(ws.a, w.fc1_w, ws.f, bias=w.fc1_b, act=L.ACT_GELU_ERF)
-            ops.gemm(ws.f, w.fc2_w, ws.x, bias=w.fc2_b, resid=ws.h1)
-        cls_rows = ws.xc  # CLS token of every image after the last layer
-        ops.layernorm_fwd(cls_rows, self.lnf[0], self.lnf[1], eps, ws.cls, None, None, rows=B)
+    def head(self, ws):
+        # the pooler reads token 0 only (modeling_vit.py:289-301), which is why the last layer ran past its attention on
+        # the CLS rows alone (encode) and left them in ws.xc; fills ws.pool (pooler_output) and ws.emb
+        ops.layernorm_fwd(ws.xc, self.lnf[0], self.lnf[1], self.c.layer_norm_eps, ws.cls, None, None, rows=ws.B)
         ops.gemm(ws.cls, self.w_pool, ws.pool, bias=self.b_pool, act=L.ACT_TANH)
         ops.l2norm_rows(ws.pool, ws.emb)
-        return ws.emb
-
-    @torch.no_grad()
-    def features(self, pixels: Tensor, normalize: bool = True) -> Tensor:
-        if pixels.dtype != torch.float32 or not pixels.is_contiguous():
-            pixels = pixels.float().contiguous()
-        ws = self.alloc(pixels.shape[0])
-        self.run(ws, pixels)
-        return (ws.emb if normalize else ws.pool).clone()
 
 
 # --------------------------------------------------------------------------- reference-shaped API (vit.py:10-137)

@@ -192,6 +192,15 @@ def accesses(name, args):
     elif name == "icap_l2norm_rows":
         dt, rows, D, x, ldx, o, ldo, _s = a
         out += [("x", x, _rows(rows, ldx, D, ES[dt])), ("out", o, _rows(rows, ldo, D, 4))]
+    elif name == "icap_clip_text_embed":
+        dt, B, L_, D, vocab, _npos, ids, tok, pos, _eos, x, prow, oov, _s = a
+        out += [("ids", ids, B * L_ * 8), ("tok", tok, vocab * D * 4), ("pos", pos, L_ * D * 4),
+                ("x", x, B * L_ * D * ES[dt]), ("pooled_row", prow, B * 4), ("oov_count", oov, 4)]
+    elif name == "icap_rows_gather":
+        dt, R, D, n_src, rows, s0, lds0, d0, ldd0, s1, lds1, d1, ldd1, _s = a
+        es = ES[dt]
+        out += [("rows", rows, R * 4), ("src0", s0, _rows(n_src, lds0, D, es)), ("dst0", d0, _rows(R, ldd0, D, es)),
+                ("src1", s1, _rows(n_src, lds1, D, es)), ("dst1", d1, _rows(R, ldd1, D, es))]
     elif name == "icap_greedy_next":
         dt, B, V, lg, ld, _eos, forced, fin, tok, ldt, step, wte, wpe, pos, D, x, _s = a
         es = ES[dt]
