@@ -80,8 +80,8 @@ fp32 C has ACT_OFF / ACT_ANY only", and gemm_plan.cpp epilogue_kind returns the 
 8-phase pairs are covered as specialised kinds; the other 19 (kind, fp32 C) pairs -- variants 0, 4, 13, 22, 26, 28 --
 do not exist as kernels, so the list runs the same arguments with an fp32 C and pins them to the dispatching
 instantiation they plan to (kind "any"; test_gemm_epi_refs_cpu.test_coverage counts 27 + 19). Variant 5 is planned
-only by the diagnostic build (test_gemm_plan_cpu.DIAG_ONLY) and is left out. The LayerNorm hand-off kinds are out of
-scope.
+only by the diagnostic build (test_gemm_plan_cpu.DIAG_ONLY) and is left out. The LayerNorm hand-off kinds (and the
+skinny kernel's fold and fused LayerNorm) are gemm_ln_refs.py's.
 
 MEASURED on an MI355X (test_gemm_epilogue_gpu.py, every element of every case; "all" = C and aux of every launch of
 the family, "C f32" = C of its fp32-C launches, the arithmetic's own figure):
