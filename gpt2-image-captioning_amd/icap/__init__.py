@@ -23,6 +23,7 @@ from .models import (ImageCaptioningModel, RetrievalAggregator, RetrievalAugment
 from .retrieval import (DeviceRetrievalStore, build_retrieval_store, create_retrieval_store,  # noqa: E402,F401
                         save_retrieval_store)
 from .evaluate import evaluate_loss, evaluate_rat_epoch, generate_and_evaluate_rat  # noqa: E402,F401
+from .metrics import DeviceCaptionMetrics  # noqa: E402,F401
 from .train import train, train_rat  # noqa: E402,F401
 from .vit import ViTConfig, ViTImageTower, extract_vit_embedding_from_image, extract_vit_embeddings, load_vit_model  # noqa: E402,F401
 from .dino import (DINOv3ImageTower, DinoConfig, extract_dino_embeddings, get_dinov3_preprocessor,  # noqa: E402,F401

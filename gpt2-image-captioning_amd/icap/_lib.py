@@ -118,6 +118,24 @@ class BeamArgs(C.Structure):
     ]
 
 
+METRIC_MAX_WORDS = 128
+METRIC_STAGE_BUILD, METRIC_STAGE_DF, METRIC_STAGE_SCORE, METRIC_STAGE_ALL = 1, 2, 4, 7
+
+
+class CaptionMetricsArgs(C.Structure):
+    _fields_ = [
+        ("n_images", i32), ("stages", i32),
+        ("sel", vp), ("img_ref_ptr", vp),
+        ("ref_ptr_a", vp), ("ref_words_a", vp), ("ref_ptr_b", vp), ("ref_words_b", vp),
+        ("hyp_ptr_a", vp), ("hyp_words_a", vp), ("hyp_ptr_b", vp), ("hyp_words_b", vp),
+        ("pair_ptr", vp),
+        ("n_vocab", i64), ("n_ref_words", i64), ("n_hyp_words", i64),
+        ("positions", i64 * 3), ("capacity", i64 * 3),
+        ("workspace", vp), ("workspace_bytes", sz),
+        ("stats", vp), ("lcs", vp), ("cider", vp), ("flag", vp),
+    ]
+
+
 JPEG_OK, JPEG_UNSUPPORTED = 0, 3
 JPEG_LOOK_BITS = 9
 JPEG_STAGE_ENTROPY, JPEG_STAGE_IDCT, JPEG_STAGE_COLOUR, JPEG_STAGE_ALL = 1, 2, 4, 7
@@ -184,6 +202,8 @@ SIGNATURES = {
     "icap_caption_score": (C.c_int, [i32, i64, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp,
                                      vp, vp, vp]),
     "icap_caption_target_ranges": (C.c_int, [i32, i32, vp, vp, vp, vp, vp]),
+    "icap_caption_metrics_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "icap_caption_metrics": (C.c_int, [vp, vp]),
     "icap_adamw_workspace_bytes": (sz, [i64]),
     "icap_adamw_step": (C.c_int, [C.POINTER(AdamWArgs), vp, vp]),
     "icap_sqnorm": (C.c_int, [i64, vp, vp, vp, vp]),

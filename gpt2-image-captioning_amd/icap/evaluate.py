@@ -2,9 +2,10 @@
 
 Generates one caption per unique image with ImageCaptioningModel.generate (KV-cached HIP
 decode) and writes the reference's predictions JSON ([{"image_id", "caption"}],
-eval.py:368-373). COCO metrics (BLEU/ROUGE-L/CIDEr via pycocoevalcap, eval.py:59-108) are
-computed only when pycocoevalcap is importable — it is outside the device hot path and is
-not installed in this image.
+eval.py:368-373). COCO metrics (BLEU/ROUGE-L/CIDEr, eval.py:59-108): by default through
+pycocoevalcap when it is importable (it is not installed in this image: no metric then);
+with `metrics="device"` through icap.metrics.DeviceCaptionMetrics, this package's own
+kernels, which need no third-party package.
 """
 
 from __future__ import annotations
@@ -56,10 +57,29 @@ def load_coco_references(annotations_path: str) -> Dict[int, list]:
     return refs
 
 
-def compute_caption_metrics(preds, annotations_path: str) -> Dict[str, float]:
+METRIC_BACKENDS = ("pycocoevalcap", "device")
+
+
+def _check_backend(backend) -> None:
+    from .metrics import DeviceCaptionMetrics
+
+    if not isinstance(backend, DeviceCaptionMetrics) and backend not in METRIC_BACKENDS:
+        raise ValueError(f'caption metrics backend must be "pycocoevalcap", "device" or a DeviceCaptionMetrics, '
+                         f'not {backend!r}')
+
+
+def compute_caption_metrics(preds, annotations_path: str, backend="pycocoevalcap") -> Dict[str, float]:
     """src/eval.py:59-108,133-157 — BLEU-1..4 / ROUGE-L / CIDEr over the images present in both predictions and
-    references (ValueError when none are), keyed as EvalMetrics.to_dict (eval.py:39-48). pycocoevalcap is not in
-    this image: without it the dict is empty (the metrics are host-side scoring, outside the device path)."""
+    references (ValueError when none are), keyed as EvalMetrics.to_dict (eval.py:39-48).
+    backend "pycocoevalcap" (the default): that package when it is importable, else an empty dict (it is not in this
+    image). backend "device": metrics.DeviceCaptionMetrics built from annotations_path, the same numbers counted by
+    this package's own kernels; a DeviceCaptionMetrics instance is used as it is (annotations_path is not read)."""
+    _check_backend(backend)
+    if backend != "pycocoevalcap":
+        from .metrics import DeviceCaptionMetrics
+
+        scorer = backend if isinstance(backend, DeviceCaptionMetrics) else DeviceCaptionMetrics(annotations_path)
+        return scorer.score(preds)
     try:
         from pycocoevalcap.bleu.bleu import Bleu
         from pycocoevalcap.cider.cider import Cider
@@ -83,14 +103,15 @@ def compute_caption_metrics(preds, annotations_path: str) -> Dict[str, float]:
 
 
 def evaluate_epoch(model, dataset, annotations_path, epoch, split_name, batch_size, num_workers, max_length,
-                   temperature, top_p, device, output_dir) -> Dict[str, Any]:
+                   temperature, top_p, device, output_dir, *, metrics="pycocoevalcap") -> Dict[str, Any]:
     """src/eval.py:311-386: predictions -> `epoch_{epoch}_{split}_predictions.json` ([{"image_id", "caption"}],
     indent 2) and `epoch_{epoch}_{split}_metrics.json` ({"epoch", "split", "num_images", **metrics}), the
-    reference's file names and layouts. Returns the metrics dict (EvalMetrics.to_dict keys)."""
+    reference's file names and layouts. Returns the metrics dict (EvalMetrics.to_dict keys). metrics: the backend
+    of compute_caption_metrics."""
     model.eval()
     os.makedirs(output_dir, exist_ok=True)
     preds = generate_predictions(model, dataset, batch_size, max_length, temperature, top_p, device)
-    m = compute_caption_metrics(preds, annotations_path) if annotations_path else {}
+    m = compute_caption_metrics(preds, annotations_path, backend=metrics) if annotations_path else {}
     with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_predictions.json"), "w") as f:
         json.dump(preds, f, indent=2)
     with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_metrics.json"), "w") as f:
@@ -100,22 +121,24 @@ def evaluate_epoch(model, dataset, annotations_path, epoch, split_name, batch_si
 
 def generate_and_evaluate_rat(model, db_store, top_k: int, top_i: int, dataset, annotations_path, batch_size: int = 32,
                               num_workers: int = 4, max_length: int = 50, temperature: float = 1.0,
-                              top_p: float = 0.9, device=None):
-    """src/eval.py:232-308: (predictions, metrics dict) of a RetrievalAugmentedTransformer over `db_store`."""
+                              top_p: float = 0.9, device=None, *, metrics="pycocoevalcap"):
+    """src/eval.py:232-308: (predictions, metrics dict) of a RetrievalAugmentedTransformer over `db_store`. metrics:
+    the backend of compute_caption_metrics."""
     model.eval()
     preds = generate_predictions(model, dataset, batch_size, max_length, temperature, top_p, device,
                                  rat=(db_store, top_k, top_i))
-    return preds, (compute_caption_metrics(preds, annotations_path) if annotations_path else {})
+    return preds, (compute_caption_metrics(preds, annotations_path, backend=metrics) if annotations_path else {})
 
 
 def evaluate_rat_epoch(model, db_store, top_k: int, top_i: int, dataset, annotations_path, epoch, split_name,
                        batch_size: int = 32, num_workers: int = 4, max_length: int = 50, temperature: float = 1.0,
-                       top_p: float = 0.9, device=None, output_dir: str = "eval_results") -> Dict[str, Any]:
+                       top_p: float = 0.9, device=None, output_dir: str = "eval_results", *,
+                       metrics="pycocoevalcap") -> Dict[str, Any]:
     """src/eval.py:391-476: evaluate_epoch for the retrieval-augmented model; the files carry the reference's
     `_rat` suffix (`epoch_{epoch}_{split}_predictions_rat.json`, `epoch_{epoch}_{split}_metrics_rat.json`)."""
     os.makedirs(output_dir, exist_ok=True)
     preds, m = generate_and_evaluate_rat(model, db_store, top_k, top_i, dataset, annotations_path, batch_size,
-                                         num_workers, max_length, temperature, top_p, device)
+                                         num_workers, max_length, temperature, top_p, device, metrics=metrics)
     with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_predictions_rat.json"), "w") as f:
         json.dump(preds, f, indent=2)
     with open(os.path.join(output_dir, f"epoch_{epoch}_{split_name}_metrics_rat.json"), "w") as f:

@@ -723,6 +723,46 @@ def caption_score(logits: Tensor, V: int, labels: Tensor, ranges: Tensor, nll: T
     return nll
 
 
+def caption_metrics_capacities(positions) -> Tuple[int, int, int]:
+    """The table capacities caption_metrics uses by default: the next power of two >= 2 x positions per order."""
+    return tuple(max(2, 1 << (2 * int(n) - 1).bit_length()) for n in positions)
+
+
+def caption_metrics_workspace(n_vocab: int, n_ref_words: int, n_hyp_words: int, capacities) -> int:
+    c = [int(v) for v in capacities]
+    return int(L.load().icap_caption_metrics_workspace_bytes(n_vocab, n_ref_words, n_hyp_words, c[0], c[1], c[2]))
+
+
+_METRIC_INT_ARRAYS = ("sel", "img_ref_ptr", "ref_ptr_a", "ref_words_a", "ref_ptr_b", "ref_words_b", "hyp_ptr_a",
+                      "hyp_words_a", "hyp_ptr_b", "hyp_words_b", "pair_ptr")
+
+
+def caption_metrics(arrays: dict, *, n_images: int, n_vocab: int, n_ref_words: int, n_hyp_words: int, positions,
+                    capacities, workspace: Tensor, stats: Tensor, lcs: Tensor, cider: Tensor, flag: Tensor,
+                    stages: int = 0) -> None:
+    """The device pass of the caption metrics (include/icap.h icap_caption_metrics). arrays: the int32 device tensors
+    named in _METRIC_INT_ARRAYS; positions / capacities: 3 ints (orders 2, 3, 4); stats int32 [n_images, 10], lcs
+    int32 [pairs], cider float64 [n_images], flag int32 [1]."""
+    a = L.CaptionMetricsArgs()
+    for name in _METRIC_INT_ARRAYS:
+        t = arrays[name]
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise L.IcapError(f"caption_metrics: {name} must be a contiguous int32 tensor")
+        setattr(a, name, t.data_ptr())
+    if stats.dtype != torch.int32 or lcs.dtype != torch.int32 or flag.dtype != torch.int32:
+        raise L.IcapError("caption_metrics: stats, lcs and flag must be int32")
+    if cider.dtype != torch.float64 or cider.numel() < n_images or stats.numel() < 10 * n_images:
+        raise L.IcapError("caption_metrics: cider must be float64 [n_images], stats int32 [n_images, 10]")
+    a.n_images, a.stages = n_images, stages
+    a.n_vocab, a.n_ref_words, a.n_hyp_words = n_vocab, n_ref_words, n_hyp_words
+    for k in range(3):
+        a.positions[k] = int(positions[k])
+        a.capacity[k] = int(capacities[k])
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.stats, a.lcs, a.cider, a.flag = stats.data_ptr(), lcs.data_ptr(), cider.data_ptr(), flag.data_ptr()
+    call("icap_caption_metrics", C.addressof(a), _stream())
+
+
 def adamw_workspace(n: int) -> int:
     return int(L.load().icap_adamw_workspace_bytes(n))
 

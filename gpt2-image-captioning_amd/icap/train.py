@@ -35,16 +35,25 @@ def train(train_dataset, model, batch_size: int, num_epochs: int, num_workers: i
           val_annotations_path: Optional[str] = None, eval_every_epoch: int = 1, eval_batch_size: Optional[int] = None,
           eval_max_length: int = 50, eval_temperature: float = 0.0, eval_top_p: float = 0.9, *, clip_model=None,
           use_graph: bool = True, log_every: int = 0, dropout: bool = True, seed: int = 0, eval_loss: bool = False,
-          select_by: str = "cider") -> dict[str, Any]:
+          select_by: str = "cider", caption_metrics: str = "pycocoevalcap") -> dict[str, Any]:
     """eval_loss: each validation epoch also scores every validation caption teacher-forced (evaluate.evaluate_loss)
     and its dict gains val_loss / val_perplexity / val_token_accuracy; the return dict gains best_val_loss.
     select_by: "cider" (the reference's rule) or "val_loss" (needs eval_loss): which metric decides the
-    best_model_epoch_{e}.pt checkpoint and best_epoch."""
+    best_model_epoch_{e}.pt checkpoint and best_epoch.
+    caption_metrics: "pycocoevalcap" (that package if importable, else no caption metric) or "device": BLEU-1..4,
+    ROUGE-L and CIDEr from metrics.DeviceCaptionMetrics, built once from val_annotations_path and used by every
+    validation epoch, so select_by="cider" selects by a real CIDEr."""
     _check_selection(eval_loss, select_by)
+    _check_caption_metrics(caption_metrics)
     return _fit(None, train_dataset, model, batch_size, num_epochs, num_workers, learning_rate, num_warmup_steps,
                 save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset, val_annotations_path,
                 eval_every_epoch, eval_batch_size, eval_max_length, eval_temperature, eval_top_p, clip_model,
-                use_graph, log_every, dropout, seed, eval_loss, select_by)
+                use_graph, log_every, dropout, seed, eval_loss, select_by, caption_metrics)
+
+
+def _check_caption_metrics(caption_metrics) -> None:
+    if caption_metrics not in ("pycocoevalcap", "device"):
+        raise ValueError(f'caption_metrics must be "pycocoevalcap" or "device", not {caption_metrics!r}')
 
 
 def _check_selection(eval_loss: bool, select_by: str) -> None:
@@ -61,13 +70,14 @@ def train_rat(train_dataset, model, db_store, top_k: int, top_i: int, batch_size
               eval_batch_size: Optional[int] = None, eval_max_length: int = 50, eval_temperature: float = 0.0,
               eval_top_p: float = 0.9, *, clip_model=None, use_graph: bool = True, log_every: int = 0,
               dropout: bool = True, seed: int = 0, eval_loss: bool = False,
-              select_by: str = "cider") -> dict[str, Any]:
+              select_by: str = "cider", caption_metrics: str = "pycocoevalcap") -> dict[str, Any]:
     """src/train.py:257-483 for a RetrievalAugmentedTransformer: train() with one added step per batch. The batch's
     image embeddings go to the device, model.augment (score GEMM, top-k, aggregate: no host synchronisation) replaces
     them by embedding + aggregated retrieval, and the fused step runs on the result. The best model is saved as
     best_rat_model_epoch_{e}.pt and validation goes through evaluate_rat_epoch. Under torch.distributed every rank
     holds a full replica of db_store on its own device."""
     _check_selection(eval_loss, select_by)
+    _check_caption_metrics(caption_metrics)
     if clip_model is not None:
         raise ValueError("train_rat takes precomputed image embeddings: retrieval augments the embedding before the "
                          "step, so clip_model (pixels inside the step's graph) is not supported")
@@ -76,13 +86,13 @@ def train_rat(train_dataset, model, db_store, top_k: int, top_i: int, batch_size
     return _fit((db_store, top_k, top_i), train_dataset, model, batch_size, num_epochs, num_workers, learning_rate,
                 num_warmup_steps, save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset,
                 val_annotations_path, eval_every_epoch, eval_batch_size, eval_max_length, eval_temperature,
-                eval_top_p, None, use_graph, log_every, dropout, seed, eval_loss, select_by)
+                eval_top_p, None, use_graph, log_every, dropout, seed, eval_loss, select_by, caption_metrics)
 
 
 def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learning_rate, num_warmup_steps,
          save_every_epoch, device, outputs_dir, grad_accum_steps, val_dataset, val_annotations_path, eval_every_epoch,
          eval_batch_size, eval_max_length, eval_temperature, eval_top_p, clip_model, use_graph, log_every, dropout,
-         seed, eval_loss=False, select_by="cider") -> dict[str, Any]:
+         seed, eval_loss=False, select_by="cider", caption_metrics="pycocoevalcap") -> dict[str, Any]:
     """The loop of train() and train_rat(); rat = (db_store, top_k, top_i) or None."""
     os.makedirs(outputs_dir, exist_ok=True)
     eval_dir = os.path.join(outputs_dir, "eval_results")
@@ -115,6 +125,11 @@ def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learnin
             trainers[key] = t
         return trainers[key]
 
+    metrics_backend = caption_metrics
+    if caption_metrics == "device" and val_dataset is not None and is_main:
+        from .metrics import DeviceCaptionMetrics
+
+        metrics_backend = DeviceCaptionMetrics(val_annotations_path, device=device)  # packed and uploaded once
     aug_out: dict[int, torch.Tensor] = {}  # augmented embeddings per batch size (train_rat)
     epoch_loss_values: list[float] = []
     val_metrics_history: list[dict[str, Any]] = []
@@ -171,11 +186,12 @@ def _fit(rat, train_dataset, model, batch_size, num_epochs, num_workers, learnin
             m = None
             if is_main and rat is None:
                 m = evaluate_epoch(model, val_dataset, val_annotations_path, epoch + 1, "val", eval_batch_size,
-                                   num_workers, eval_max_length, eval_temperature, eval_top_p, device, eval_dir)
+                                   num_workers, eval_max_length, eval_temperature, eval_top_p, device, eval_dir,
+                                   metrics=metrics_backend)
             elif is_main:
                 m = evaluate_rat_epoch(model, rat[0], rat[1], rat[2], val_dataset, val_annotations_path, epoch + 1,
                                        "val", eval_batch_size, num_workers, eval_max_length, eval_temperature,
-                                       eval_top_p, device, eval_dir)
+                                       eval_top_p, device, eval_dir, metrics=metrics_backend)
             if is_main and eval_loss:  # every validation caption teacher-forced, totals on the device
                 from .evaluate import LOSS_KEYS, evaluate_loss
 

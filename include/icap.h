@@ -400,6 +400,71 @@ int icap_caption_target_ranges(int32_t B, int32_t S, const int32_t* row_slot, co
                                const int32_t* seq_len, int32_t* ranges, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Caption metrics: the exact parts of corpus BLEU-1..4, ROUGE-L and CIDEr    */
+/* (pycocoevalcap's Bleu(4), Rouge(), Cider(n = 4, sigma = 6) on raw strings) */
+/* for n_images scored images, one hypothesis and m >= 1 references each.     */
+/* The host tokenises and finishes (icap/metrics.py); words are int32 ids     */
+/* below n_vocab from one dictionary. Two tokenisations are carried:          */
+/*   _a  str.split()     BLEU and CIDEr                                       */
+/*   _b  str.split(" ")  ROUGE-L (the empty token is an ordinary word)        */
+/* Every array is device int32. Packed captions: words [n] with row pointers  */
+/* [rows + 1]; a caption has at most ICAP_METRIC_MAX_WORDS words (the kernels */
+/* read no further). References: image i of the corpus owns the contiguous    */
+/* rows img_ref_ptr[i] .. img_ref_ptr[i+1]-1. Scored image j is corpus image  */
+/* sel[j]; hypothesis row j belongs to it; pair_ptr [n_images + 1] is the     */
+/* running count of its references (where its lcs values start).              */
+/* Outputs: stats int32 [n_images][10] = testlen, reflen (closest, a tie to   */
+/* the shorter), guess[4], correct[4]; lcs int32 [pair_ptr[n_images]], the    */
+/* longest common subsequence of hypothesis and reference on the _b tokens;   */
+/* cider double [n_images], 10 * mean over orders of the summed similarities  */
+/* over m, with N = n_images and the document frequencies of the scored       */
+/* images' references; flag int32 [1], nonzero if a table filled up (only     */
+/* when positions understates the corpus).                                    */
+/* n-gram identity is exact: the id of a k-gram is the slot of the key        */
+/* (id of its (k-1)-gram prefix) << 32 | last word in the open-addressing     */
+/* table of order k, claimed by one 64-bit compare-and-swap. capacity[k] (for */
+/* orders 2, 3, 4) is a power of two GREATER than positions[k], the number of */
+/* k-gram start positions in the scored hypotheses and references;            */
+/* ICAP_ERR_ARG otherwise, before any launch. No thread waits on another and  */
+/* every probe loop ends after capacity steps. Integer atomics and fixed-order */
+/* fp64 sums: two runs give the same bits. stages: 0 or                        */
+/* ICAP_METRIC_STAGE_ALL runs the pass; a single stage runs that part alone   */
+/* on the workspace the earlier ones left (tools/caption_metrics_bench.py).   */
+/* Runs on the stream; allocates nothing and synchronises nothing.            */
+/* ------------------------------------------------------------------------- */
+#define ICAP_METRIC_MAX_WORDS 128
+enum { ICAP_METRIC_STAGE_BUILD = 1, ICAP_METRIC_STAGE_DF = 2, ICAP_METRIC_STAGE_SCORE = 4, ICAP_METRIC_STAGE_ALL = 7 };
+typedef struct icap_caption_metrics_args {
+  int32_t n_images;
+  int32_t stages;
+  const int32_t* sel;          /* [n_images] */
+  const int32_t* img_ref_ptr;  /* [corpus images + 1] */
+  const int32_t* ref_ptr_a;    /* [reference rows + 1] */
+  const int32_t* ref_words_a;  /* [n_ref_words] */
+  const int32_t* ref_ptr_b;
+  const int32_t* ref_words_b;
+  const int32_t* hyp_ptr_a;    /* [n_images + 1] */
+  const int32_t* hyp_words_a;  /* [n_hyp_words] */
+  const int32_t* hyp_ptr_b;
+  const int32_t* hyp_words_b;
+  const int32_t* pair_ptr;     /* [n_images + 1] */
+  int64_t n_vocab;
+  int64_t n_ref_words;         /* length of ref_words_a (the whole corpus) */
+  int64_t n_hyp_words;         /* length of hyp_words_a */
+  int64_t positions[3];        /* orders 2, 3, 4 */
+  int64_t capacity[3];
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t* stats;
+  int32_t* lcs;
+  double* cider;
+  int32_t* flag;
+} icap_caption_metrics_args;
+size_t icap_caption_metrics_workspace_bytes(int64_t n_vocab, int64_t n_ref_words, int64_t n_hyp_words, int64_t cap2,
+                                            int64_t cap3, int64_t cap4);
+int icap_caption_metrics(const icap_caption_metrics_args* args, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Global grad-norm clip + AdamW + linear LR schedule over ONE flat fp32       */
 /* parameter buffer (src/train.py:94-103,150-159; TORCH/nn/utils/clip_grad.py */
 /* :121-186; TORCH/optim/adam.py:419,457,476,499,545-547;                       */
